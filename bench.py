@@ -24,8 +24,15 @@ c4 / c5 run through the drivers' own engine (jobs.JobSet): every cell / pair sha
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  The CPU oracle is used only for the `cpu_baseline` leg (rank 0, N=1, a bounded sample of
-the same workload) and is never on the measured path.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it; `--full` adds what takes runs of
+its own: the `cpu_baseline` leg (rank 0, N=1, the CPU oracle on a bounded sample of the same workload, compared with the GPU
+output), never on the measured path.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the path receives it, to DIR/<name>.npy (float64)
+before the line is printed: rank 0's chains (c2 / c3) or the reduced per-job results (c4 / c5) and the node-level summary
+(columns in SUMMARY_FIELDS order).  All files together stay under DUMP_BYTES: an array that does not fit its share is replaced by
+a fixed, seeded sample of its elements in C order, whose flat indices go to DIR/<name>_index.npy.  The inputs are fixed by the
+arguments, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import hashlib
@@ -44,6 +51,75 @@ VALU_PEAK_GINST = 256 * 4 * 2.4 / 2  # 256 CUs x 4 SIMD-32 x 2.4 GHz / 2 cycles 
 METRIC = "Metropolis moves/sec (whole node) + min-energy-reached, N=12 board MCMC"
 KERNEL_SOURCE = os.path.join(ROOT, "monte-carlo-collective_amd", "csrc", "mcq_hip.hip")
 C5_PAIRS = [(s, e) for s in (0.1, 0.5, 1.0, 2.0) for e in (2.0, 3.0, 5.0, 8.0)]  # BASELINE fixes only the count
+SUMMARY_FIELDS = ("n_chains", "accepted", "proposed", "sum_best", "sumsq_best", "sum_steps_to_best", "min_best", "mean_best", "std_best",
+                  "mean_steps_to_best", "acceptance_rate")  # distributed.summary_from_counters; a missing min_best is NaN
+DUMP_BYTES = 60 << 20  # --dump-outputs: all files together (headers and index files included) stay below 64 MiB
+DUMP_SEED = 1234       # the element sample of an array that does not fit its share: fixed, so that runs compare file by file
+
+
+def dump_outputs(out_dir, fields):
+    """Write {name: (shape, take)} to out_dir/<name>.npy as float64; take(flat) returns the values at the flat (C order) indices
+    `flat` of the logical array.  The budget is shared out smallest array first; an array that does not fit its share is sampled."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    todo = sorted(fields.items(), key=lambda kv: (int(np.prod(kv[1][0])), kv[0]))
+    left = DUMP_BYTES
+    for i, (name, (shape, take)) in enumerate(todo):
+        size = int(np.prod(shape))
+        share = left // (len(todo) - i) - 256  # room for the .npy headers
+        if 8 * size <= share:
+            idx = None
+            vals = np.asarray(take(np.arange(size)), dtype=np.float64).reshape(shape)
+        else:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, size, max(1, share // 16)))
+            vals = np.asarray(take(idx), dtype=np.float64)
+            np.save(os.path.join(out_dir, f"{name}_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), vals)
+        left -= vals.nbytes + (0 if idx is None else idx.nbytes) + 256
+
+
+def summary_row(sm):
+    return [float("nan") if sm[k] is None else float(sm[k]) for k in SUMMARY_FIELDS]
+
+
+def run_fields(run, n_steps, abi):
+    """dump_outputs fields of a DeviceRun's outputs.  energy_hist is cut to its n_steps + 1 columns and accept_bits unpacked to one
+    0 / 1 per step; entries past a chain's history (early stop) are 0 rather than whatever the buffer held."""
+    import numpy as np
+    import torch
+
+    dt = abi.OUTPUT_DTYPES
+    t, n = run.t, int(run.p.n_chains)
+
+    def gather(k, flat):  # values of the buffer run.t[k] at physical flat indices, in the output's own dtype
+        a = t[k].reshape(-1)[torch.from_numpy(np.asarray(flat, dtype=np.int64)).to(t[k].device)].cpu().numpy()
+        return a.view(dt[k]) if dt[k] in (np.uint64, np.uint32) else a
+
+    fields = {}
+    for k, v in t.items():
+        if k not in ("energy_hist", "accept_bits"):
+            fields[k] = (tuple(v.shape), lambda flat, k=k: gather(k, flat))
+    if "energy_hist" in t:
+        L, stride = n_steps + 1, t["energy_hist"].shape[1]
+        hist_len = t["hist_len"].cpu().numpy()
+
+        def hist(flat):
+            r, c = flat // L, flat % L
+            return np.where(c < hist_len[r], gather("energy_hist", r * stride + c), 0)
+
+        fields["energy_hist"] = ((n, L), hist)
+    if "accept_bits" in t:
+        words = t["accept_bits"].shape[1]
+        executed = t["steps_executed"].cpu().numpy()
+
+        def accept(flat):
+            r, c = flat // n_steps, flat % n_steps
+            w = gather("accept_bits", r * words + c // 64)
+            return np.where(c < executed[r], (w >> (c % 64).astype(np.uint64)) & np.uint64(1), 0)
+
+        fields["accept_bits"] = ((n, n_steps), accept)
+    return fields
 
 
 def kernel_sha():
@@ -286,8 +362,12 @@ def bench_single(args, torch, mcq_amd, dist, rank, world, red_dev):
         },
     }
     roofline_from_pmc(line, pmc, why, sweep_avg_ms, algo_bytes, local_moves)
+    if args.dump_outputs and rank == 0:
+        fields = run_fields(run, args.n_steps, abi)
+        fields["summary"] = ((len(SUMMARY_FIELDS),), lambda flat: np.asarray(summary_row(sm))[flat])
+        dump_outputs(args.dump_outputs, fields)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import oracle  # checker / baseline only; never on the measured path
 
         threads = args.cpu_threads or usable_cpus()
@@ -415,6 +495,14 @@ def bench_jobs(args, torch, mcq_amd, dist, rank, world, red_dev):
         r0 = res[0]
         mean, std = jb.mean_std_from_sums(r0["step_sum"], r0["step_sumsq"], r0["step_count"])
         line["first_pair_mean_energy_at"] = {str(e): float(mean[e]) for e in (0, n // 4, n // 2, n)}
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+
+        per_job = {"summary": [summary_row(r["summary"]) for r in res]}
+        for k in ("best_energy", "steps_to_best") + (mcq_amd.distributed.STAT_FIELDS if want == "stats" else ()):
+            per_job[k] = [r[k] for r in res]
+        arrays = {k: np.array(v, dtype=np.float64) for k, v in per_job.items()}  # [job, ...]
+        dump_outputs(args.dump_outputs, {k: (a.shape, lambda flat, a=a: a.reshape(-1)[flat]) for k, a in arrays.items()})
     return line
 
 
@@ -440,10 +528,15 @@ def main():
     ap.add_argument("--replicas", type=int, default=16, help="rungs of a ladder (2, 4, 8, 16)")
     ap.add_argument("--ladder", default="0.7,1.4", help="beta multipliers of the lowest and highest rung (geometric in between)")
     ap.add_argument("--no-states", action="store_true", help="c2 / c3: no best_state / final_state outputs (what the drivers' engine runs with)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own: the cpu_baseline leg (c2 / c3, one rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64, < 64 MiB in all; see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-chains", type=int, default=1024)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the cpu_baseline leg (0 = every CPU this process may use)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.chains is None:
         args.chains = 65536 if args.config in ("c2", "c3") else 1024
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:

@@ -49,7 +49,8 @@ def test_two_ranks_equal_one_rank():
         assert set(line["per_rank"]) == {"init_ms", "sweep_ms", "reduce_ms", "step_ms"}
         assert all(len(v) == n and all(x > 0 for x in v) for v in line["per_rank"].values())
         assert line["allreduce"]["per_step"] == 1 and line["allreduce"]["payload_bytes"] == 8 * (6 + n)
-        assert "gpu_max_hw_queues" in line["config"] and line["config"]["gpu_max_hw_queues"] is None  # c2: one stream, nothing raised
+        # c2: one stream, nothing raised -- the value in force is the one the bench inherited (None when the environment sets none)
+        assert "gpu_max_hw_queues" in line["config"] and line["config"]["gpu_max_hw_queues"] == os.environ.get("GPU_MAX_HW_QUEUES")
     assert two["allreduce"]["backend"] == "gloo" and one["allreduce"]["backend"].startswith("none")
 
 

@@ -10,7 +10,7 @@ cd $ROOT
 J="python $ROOT/tools/last_json_line.py"
 step() { echo "=== $1"; shift; timeout -k 10 ${STEP_TIMEOUT:-600} bash -o pipefail -c "$*"; rc=$?; echo "=== rc=$rc"; if [ $rc -eq 124 ] || [ $rc -ge 128 ]; then echo "killed: stopping"; exit $rc; fi; }
 
-step "headline bench (with cpu baseline)" "python bench.py > $OUT/bench.json && tail -c 600 $OUT/bench.json"
+step "headline bench (with cpu baseline)" "python bench.py --full > $OUT/bench.json && tail -c 600 $OUT/bench.json"
 step "kernel trace stats of the same command" "cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kernel_stats -- python $ROOT/bench.py --no-cpu-baseline > $OUT/kernel_stats_bench.json 2> $OUT/kernel_stats.err; ls $OUT/kernel_stats/*/ | head"
 step "PMC refresh, headline" "tools/pmc_refresh.sh gpurun_out/${R}_evidence/pmc_headline"
 step "PMC, full_3d (config 3)" "tools/pmc_refresh.sh gpurun_out/${R}_evidence/pmc_c3 --steps 1 --warmup 0 --no-cpu-baseline --config c3"

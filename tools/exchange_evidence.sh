@@ -12,4 +12,4 @@ run --exchange 1 --ladder 0.7,1.4
 run --exchange 64 --ladder 0.7,1.4 --replicas 4
 run --config c3
 run --config c3 --exchange 64 --ladder 0.7,1.4 --replicas 8
-python $ROOT/bench.py --steps 1 --warmup 0 --exchange 64 --ladder 0.7,1.4 --cpu-chains 256 | $J
+python $ROOT/bench.py --full --steps 1 --warmup 0 --exchange 64 --ladder 0.7,1.4 --cpu-chains 256 | $J
