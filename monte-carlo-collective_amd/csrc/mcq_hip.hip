@@ -115,10 +115,7 @@ constexpr int MT_N = 624;
 constexpr int MT_M = 397;
 constexpr int RING = 64;          // ready (tempered) words per chain
 constexpr int RING_MIRROR = 32;   // slots 0..31 are repeated behind the ring: a proposal reads up to 31 slots past pos without wrapping
-#ifndef MCQ_RED_STRIPES
-#define MCQ_RED_STRIPES 8
-#endif
-constexpr int RED_STRIPES = MCQ_RED_STRIPES;  // trace == REDUCED: independent accumulator copies, so one address sees few atomics
+constexpr int RED_STRIPES = 8;    // trace == REDUCED: independent accumulator copies, so one address sees few atomics
 constexpr int REC_MIRROR = 624;   // record word: copy of MT word 0, so that words i+1 and i+397.. of a block never wrap inside a lane's run
 constexpr int REC_POS = 625;      // record word: MT index of the next word to consume
 constexpr int REC_GEN_END = 626;  // record word: words [0, gen_end) belong to the current generation
@@ -698,19 +695,6 @@ struct Stream {
 
     // MT word `idx` of this chain: uniform base + 32-bit offset, so the address needs no 64-bit vector math
     __device__ __forceinline__ uint32_t* word(int idx) const { return (uint32_t*)(wbase + (coff + 4u * (uint32_t)idx)); }
-    // Timing experiments (tools/exp_build.sh; never defined in the shipped library, results are wrong with any of them):
-    // MCQ_EXP_HOT_LOADS / MCQ_EXP_HOT_STORES fold the block's reads / writes onto the first 64 words of the record (cache-resident),
-    // MCQ_EXP_NO_STORE drops the write-back, MCQ_EXP_NT_STORE / MCQ_EXP_NT_XLOAD mark the stream's accesses non-temporal.
-#ifdef MCQ_EXP_HOT_LOADS
-    __device__ __forceinline__ uint32_t* lword(int idx) const { return word(idx & 63); }
-#else
-    __device__ __forceinline__ uint32_t* lword(int idx) const { return word(idx); }
-#endif
-#ifdef MCQ_EXP_HOT_STORES
-    __device__ __forceinline__ uint32_t* sword(int idx) const { return word(idx & 63); }
-#else
-    __device__ __forceinline__ uint32_t* sword(int idx) const { return word(idx); }
-#endif
 
     // load the inputs of block gi: words i, i+1 and (i+397) mod 624 for the lane's WPL words.  Word 624 of the record
     // mirrors word 0 (the NEW word 0, regenerated earlier in the same pass), which is what index 624 stands for in both
@@ -724,36 +708,25 @@ struct Stream {
             // two runs of four: each half of (i+397) mod 624 wraps on its own (the first can run over the end by the one mirrored
             // word, at i0 = 224; the second then starts at word 1)
             const int ix1 = i0 + 4 + MT_M >= MT_N ? i0 + 4 + MT_M - MT_N : i0 + 4 + MT_M;
-            const uint4 q0 = *(const uint4*)lword(i0), q1 = *(const uint4*)lword(i0 + 4);
+            const uint4 q0 = *(const uint4*)word(i0), q1 = *(const uint4*)word(i0 + 4);
             pa[0] = q0.x, pa[1] = q0.y, pa[2] = q0.z, pa[3] = q0.w, pa[4] = q1.x, pa[5] = q1.y, pa[6] = q1.z, pa[7] = q1.w;
-            const W4 x0 = *(const W4*)lword(ix0), x1 = *(const W4*)lword(ix1);
+            const W4 x0 = *(const W4*)word(ix0), x1 = *(const W4*)word(ix1);
             px[0] = x0.x, px[1] = x0.y, px[2] = x0.z, px[3] = x0.w, px[4] = x1.x, px[5] = x1.y, px[6] = x1.z, px[7] = x1.w;
         } else if constexpr (WPL == 4) {
-#ifdef MCQ_EXP_NT_CUR
-            typedef uint32_t u32x4a __attribute__((ext_vector_type(4)));
-            const u32x4a q = __builtin_nontemporal_load((const u32x4a*)lword(i0));
-#else
-            const uint4 q = *(const uint4*)lword(i0);
-#endif
+            const uint4 q = *(const uint4*)word(i0);
             pa[0] = q.x, pa[1] = q.y, pa[2] = q.z, pa[3] = q.w;
-#ifdef MCQ_EXP_NT_XLOAD
-            typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(4)));
-            const u32x4u xx = __builtin_nontemporal_load((const u32x4u*)lword(ix0));
-            px[0] = xx.x, px[1] = xx.y, px[2] = xx.z, px[3] = xx.w;
-#else
-            const W4 x = *(const W4*)lword(ix0);
+            const W4 x = *(const W4*)word(ix0);
             px[0] = x.x, px[1] = x.y, px[2] = x.z, px[3] = x.w;
-#endif
         } else if constexpr (WPL == 2) {
-            const uint2 q = *(const uint2*)lword(i0);
+            const uint2 q = *(const uint2*)word(i0);
             pa[0] = q.x, pa[1] = q.y;
-            const W2 x = *(const W2*)lword(ix0);
+            const W2 x = *(const W2*)word(ix0);
             px[0] = x.x, px[1] = x.y;
         } else {
-            pa[0] = *lword(i0);
-            px[0] = *lword(ix0);
+            pa[0] = *word(i0);
+            px[0] = *word(ix0);
         }
-        pn = *lword(i0 + WPL);
+        pn = *word(i0 + WPL);
         pending = true;
     }
 
@@ -824,24 +797,12 @@ struct Stream {
         uint32_t* slot = ring + so + gl * WPL;
         uint32_t* mirror = ring + (so < RING_MIRROR ? so + RING : so) + gl * WPL;  // mirror of slots 0..31 (otherwise the same store again)
         if constexpr (WPL == 8) {
-            *(uint4*)sword(i0) = make_uint4(v[0], v[1], v[2], v[3]), *(uint4*)sword(i0 + 4) = make_uint4(v[4], v[5], v[6], v[7]);
+            *(uint4*)word(i0) = make_uint4(v[0], v[1], v[2], v[3]), *(uint4*)word(i0 + 4) = make_uint4(v[4], v[5], v[6], v[7]);
             *(uint4*)slot = make_uint4(t[0], t[1], t[2], t[3]), *(uint4*)(slot + 4) = make_uint4(t[4], t[5], t[6], t[7]);
             if constexpr (MIRROR) *(uint4*)mirror = make_uint4(t[0], t[1], t[2], t[3]), *(uint4*)(mirror + 4) = make_uint4(t[4], t[5], t[6], t[7]);
             bits = (flags4(t[0], t[1], t[2], t[3]) | (flags4(t[4], t[5], t[6], t[7]) << 4)) << (gl * 8);
         } else if constexpr (WPL == 4) {
-#if defined(MCQ_EXP_NO_STORE)
-#elif defined(MCQ_EXP_NT_STORE)
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            __builtin_nontemporal_store((u32x4){v[0], v[1], v[2], v[3]}, (u32x4*)sword(i0));
-#elif defined(MCQ_EXP_LAST_TOUCH)
-            // timing experiment (profiles/r03_last_touch.txt): records are 128-byte aligned in this build, so the block with gi & 16
-            // is the second half of its line -- after its write-back the line is dead for ~100 steps: a streaming store for that one
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            if (gi & 16) __builtin_nontemporal_store((u32x4){v[0], v[1], v[2], v[3]}, (u32x4*)sword(i0));
-            else *(uint4*)sword(i0) = make_uint4(v[0], v[1], v[2], v[3]);
-#else
-            *(uint4*)sword(i0) = make_uint4(v[0], v[1], v[2], v[3]);
-#endif
+            *(uint4*)word(i0) = make_uint4(v[0], v[1], v[2], v[3]);
             *(uint4*)slot = make_uint4(t[0], t[1], t[2], t[3]);
             if constexpr (MIRROR) *(uint4*)mirror = make_uint4(t[0], t[1], t[2], t[3]);
             bits = flags4(t[0], t[1], t[2], t[3]) << (gl * 4);
@@ -984,11 +945,7 @@ __device__ __forceinline__ void reduce_block(const uint32_t* wave_stage, int cha
         sq += ((unsigned long long)(uint32_t)__shfl_xor((int)(sq >> 32), off, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)sq, off, 64);
     }
     const long long idx = (long long)e0 + ent;
-#ifdef MCQ_EXP_NO_ATOMICS
-    if (lane < 16 && idx < n_entries && (ac | cn) == 0xffffffffu) {
-#else
     if (lane < 16 && idx < n_entries && (ac | cn) != 0) {
-#endif
         atomicAdd(red + idx, (unsigned long long)se);
         atomicAdd(red + red_len + idx, sq);
         atomicAdd(red + 2 * red_len + idx, (unsigned long long)ac | ((unsigned long long)cn << 32));
@@ -1103,14 +1060,9 @@ __device__ __forceinline__ void copy_state_out(uint8_t* dst, const uint8_t* hts,
 // wavefront), and the queens -- i | j << 8 | k << 16 in 32-bit entries -- stay in the workspace's table like SLIM's.
 template <int MODE, int G, bool PATIENCE, int NT, bool REDUCED, bool PHILOX = false, int NC = 0, bool EXCH = false, bool CAND5 = false, bool EARLYU = false, bool SLIM = false, bool CNT = false,
           bool WIDE = false>
-#ifndef MCQ_EXP_WAVES  // experiment (profiles/r03_occupancy5.txt): the register budget of more wavefronts per SIMD
-#define MCQ_EXP_WAVES 4
-#endif
+// (the register budget of four wavefronts per SIMD: that of five made the headline kernel 18 % slower, profiles/r03_occupancy5.txt)
 // (G = 2: 32 chains per wavefront take twice the LDS of 16, so a CU holds two of those wavefronts per SIMD, and each may use the registers of two)
-#ifndef MCQ_G2_WAVES
-#define MCQ_G2_WAVES 2
-#endif
-__global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3D && G == 4 && NT > 0 && !SLIM) ? 2 : (SLIM && NT > 6) ? 3 : MCQ_EXP_WAVES) void mcq_sweep_kernel(KArgs a) {
+__global__ __launch_bounds__(64, G == 2 ? 2 : (MODE == MCQ_MODE_FULL3D && G == 4 && NT > 0 && !SLIM) ? 2 : 4) void mcq_sweep_kernel(KArgs a) {
     static_assert(!SLIM || (MODE == MCQ_MODE_FULL3D && NT > 0 && !PATIENCE), "the slim layout exists for the unrolled full_3d kernels");
     static_assert(!WIDE || (MODE == MCQ_MODE_FULL3D && NT == 0 && NC == 0 && G == 16 && !SLIM), "64-bit column words: the run-time-loop full_3d kernel at 16 lanes per chain");
     static_assert(!CNT || (MODE == MCQ_MODE_BOARD && G == 4 && NT == 0 && !EXCH), "line counters: boards at 4 lanes per chain");
@@ -1228,10 +1180,7 @@ __global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3
     uint32_t accw = 0;  // accept bits of the current block of 32 steps
     const bool exact_only = (a.flags & MCQ_FLAG_EXACT_EXP) != 0;
     // half-width of the float32 bracket around exp(x) 2^27 as w = e27 * w_scale + w_bias; MCQ_FLAG_EXACT_EXP makes it cover everything
-#ifndef MCQ_W_SCALE_BITS
-#define MCQ_W_SCALE_BITS 0x3a800000u /* 2^-10 */
-#endif
-    uint32_t w_scale_bits = exact_only ? 0u : MCQ_W_SCALE_BITS, w_bias_bits = exact_only ? 0x7f61b1e6u /* 3.0e38 */ : 0x3f000000u /* 0.5 */;
+    uint32_t w_scale_bits = exact_only ? 0u : 0x3a800000u /* 2^-10 */, w_bias_bits = exact_only ? 0x7f61b1e6u /* 3.0e38 */ : 0x3f000000u /* 0.5 */;
     asm volatile("" : "+s"(w_scale_bits), "+s"(w_bias_bits));  // two scalars, no select per step
     const float w_scale = __uint_as_float(w_scale_bits), w_bias = __uint_as_float(w_bias_bits);
     const bool force_slow = (a.flags & MCQ_FLAG_SEQUENTIAL_DRAWS) != 0;
@@ -1320,11 +1269,7 @@ __global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3
     // Sizes whose randint(0, N) rejects many words (N / (mask + 1) < 0.6: N = 9, 17, 18, 19) look further ahead for their five
     // accepted words and run into a short ring more often: their mark is 28 (lone wavefront, 20 000 steps: N = 9 13.4 -> 12.7 ms,
     // N = 17 19.4 -> 18.1 ms, N = 18 18.1 -> 17.5 ms; every other size loses 1-2 % at 28: profiles/r03_low_water.txt).  A run-time scalar.
-#ifdef MCQ_LOW_WATER
-    const uint32_t LOW_WATER = MCQ_LOW_WATER;
-#else
     const uint32_t LOW_WATER = (uint32_t)a.low_water;
-#endif
 
     // replica exchange: the chain's rung, the float32 image of its beta multiplier, accepted swaps; wave-uniform countdown and parity
     int rung = EXCH ? grp % a.exch_R : 0, n_exch = 0;
@@ -1451,14 +1396,8 @@ __global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3
             // device LOSES 4 % (552 against 531 ms: twelve more live registers across the draw), so the launcher picks the variant by the
             // wavefronts the launch puts on a SIMD.  With the reduced trace the packed variants request early too since round 3:
             // +0.9 % at N = 12.  profiles/r03_early_probes.txt)
-#ifdef MCQ_EXP_NO_EARLY  // timing experiment: no early requests at all
-            constexpr bool EARLY_PROBES = false;
-#else
-#ifndef MCQ_G2_EARLY_NT  // (two lanes per chain: the register budget of two wavefronts per SIMD holds the probed heights of up to eight passes)
-#define MCQ_G2_EARLY_NT 8
-#endif
-            constexpr bool EARLY_PROBES = MODE == MCQ_MODE_BOARD && NT >= 1 && NT <= (G == 2 ? MCQ_G2_EARLY_NT : 3) && (PACKED || EARLYU);
-#endif
+            // (two lanes per chain: the register budget of two wavefronts per SIMD holds the probed heights of up to eight passes)
+            constexpr bool EARLY_PROBES = MODE == MCQ_MODE_BOARD && NT >= 1 && NT <= (G == 2 ? 8 : 3) && (PACKED || EARLYU);
             uint32_t ph[4 * NTP];
             // (`mark`: 0 where the probes are requested early, an opaque zero in the rare path's second request.  With two plain requests the
             // compiler merges the byte loads as 8-bit values and widens them again behind the merge: twelve `v_and 0xff` per step in the common
@@ -1564,15 +1503,7 @@ __global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3
                 // (SLIM: a 2-byte read from global memory at the head of the step's dependency chain.  Requesting it a whole step ahead --
                 // the position of the next step's first randint(0, Q) word is known once a step's draws are done -- measured nothing at four
                 // wavefronts per SIMD: 232.8 against 232.4 ms, profiles/r04_full3d_slim.txt)
-#if defined(MCQ_EXP_QN_SC1)  // timing experiment: the queen read with agent scope (sc1): does the L2 then ask the fabric for less than a 128-byte line?
-                if constexpr (SLIM) oldp = __hip_atomic_load(qn + qi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else oldp = qn[qi];
-#elif defined(MCQ_EXP_QN_NT)
-                if constexpr (SLIM) oldp = __builtin_nontemporal_load(qn + qi);
-                else oldp = qn[qi];
-#else
                 oldp = qn[qi];
-#endif
                 pa = (int)(w1 & maskN), pb = (int)(w2 & maskN), pc = (int)((w3 & maskN) & QM);
                 // (WIDE: an attempt that is not used may hold any value up to the mask, 63 -- at N = 33 a column index far behind the chain's table,
                 // and for the wavefront's last chain behind the workgroup's LDS: clamped, here and for the other two triples)
@@ -1874,15 +1805,7 @@ __global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3
                 const bool same_column = op_i == (uint32_t)pa && op_j == (uint32_t)pb;
                 colw[times_N<NC>((int)op_i, N) + (int)op_j] = (colw_t)cleared;
                 colw[times_N<NC>(pa, N) + pb] = (colw_t)((same_column ? cleared : cw_new) | ((cword_t)1 << pc));
-#if defined(MCQ_EXP_QN_SC1)
-                if constexpr (SLIM) __hip_atomic_store(qn + qi, (uint16_t)newp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else qn[qi] = (qn_t)newp;
-#elif defined(MCQ_EXP_QN_NT)
-                if constexpr (SLIM) __builtin_nontemporal_store((uint16_t)newp, qn + qi);
-                else qn[qi] = (qn_t)newp;
-#else
                 qn[qi] = (qn_t)newp;
-#endif
             }
             E += __mul24((int)acc, dE);  // E += acc ? dE : 0  (|dE| <= 8 N)
             const bool improved = E < best;  // only an accepted move can get below the best so far (E >= best otherwise)
@@ -1919,10 +1842,7 @@ __global__ __launch_bounds__(64, G == 2 ? MCQ_G2_WAVES : (MODE == MCQ_MODE_FULL3
                     cold[C_N_ACC] += __popc(accw);  // accepted moves are counted from the bit words
                     if (have_bits && gl == 0) __builtin_nontemporal_store(accw, bits_at((e >> 5) - 1));
                     accw = 0;
-#ifndef MCQ_PACE_MASK
-#define MCQ_PACE_MASK 63
-#endif
-                    if ((e & MCQ_PACE_MASK) == 0 && a.pace) {
+                    if ((e & 63) == 0 && a.pace) {
                         // Pacing: publish this wavefront's progress, read the row of its SIMD, and take a priority that grows with
                         // the number of co-resident wavefronts that are further along (ties fall to the arbiter's age order).
                         const uint32_t mine = (uint32_t)e;
@@ -2306,11 +2226,7 @@ int queens_of(const mcq_params* p) { return p->mode == MCQ_MODE_FULL3D && p->n_q
 size_t state_bytes_of(const mcq_params* p) { return p->mode == MCQ_MODE_BOARD ? (size_t)p->N * p->N : (size_t)3 * queens_of(p); }
 
 // 64-byte multiple: the sweep reads and writes the MT words of a record in aligned 64-byte blocks
-#if defined(MCQ_EXP_LAST_TOUCH) || defined(MCQ_EXP_REC128)  // timing experiment: 128-byte records, so that a block's half of its line is known from its index
-int rec_words_for(const mcq_params* p) { return (REC_STATE + (int)((state_bytes_of(p) + 3) / 4) + 31) & ~31; }
-#else
 int rec_words_for(const mcq_params* p) { return (REC_STATE + (int)((state_bytes_of(p) + 3) / 4) + 15) & ~15; }
-#endif
 
 // full_3d: entries per chain of the packed queen table in the workspace (64-byte rows; uint16 entries, uint32 beyond N = 32); 0 for boards
 int qtab_stride_for(const mcq_params* p) { return p->mode == MCQ_MODE_FULL3D ? (queens_of(p) + 31) & ~31 : 0; }
@@ -2388,11 +2304,7 @@ int chain_lds_words_for(int N, int mode, bool narrow, int Q = 0, bool slim = fal
     // The chains of a wavefront make many accesses at the SAME offset of their slices (history staging, cold scalars, ring appends):
     // a stride of 4 mod 8 words puts the 8 chains of a 32-lane access group on 8 different banks; 0 mod 8 would serialise them
     // (A/B on the headline problem, same box: profiles/r02_lds_stride_ab.txt, r02_lds_stride_pmc.txt).
-#ifdef MCQ_EXP_LDS_STRIDE_0MOD8  // timing experiment (tools/exp_build.sh): the conflicting stride, for the A/B in profiles/
-    w = (w + 7) & ~7;
-#else
     if (w % 8 == 0) w += 4;
-#endif
     return w;
 }
 
@@ -2575,13 +2487,6 @@ int launch_sweep_g(const KArgs& a, hipStream_t s) {
             // the slim layout (N = 9..12): two lanes around each of the two cells, ceil(N / 2) unrolled passes, the queens in global memory.
             // (65 536 chains x 20 000 steps against 8 lanes: N = 9 53.2 / 65.4 ms, N = 10 49.6 / 62.6, N = 11 60.3 / 62.9, N = 12 52.1 / 59.8;
             // seven and eight passes spill and lose -- N = 13 129 / 68 ms, N = 16 109 / 91: profiles/r04_full3d_slim.txt)
-#ifdef MCQ_EXP_SLIM16  // experiment: seven and eight passes (N = 13..16) at the register budget of three wavefronts per SIMD, which is all their LDS allows anyway
-            if (!a.red && a.N > 12 && a.N <= 16) {
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q, true);
-                return (a.N + 1) / 2 == 7 ? launch_sweep<MODE, G, false, 7, false, false, 0, false, false, false, true>(b, s) : launch_sweep<MODE, G, false, 8, false, false, 0, false, false, false, true>(b, s);
-            }
-#endif
             if (a.N > 8 && a.N <= 12) {
                 KArgs b = a;
                 b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q, true);
@@ -2640,7 +2545,6 @@ int launch_sweep_g(const KArgs& a, hipStream_t s) {
                 return a.N <= 4 ? launch_sweep<MODE, G, false, 1, false, false, 0, false, true>(a, s) : launch_sweep<MODE, G, false, 2, false, false, 0, false, true>(a, s);
             if (!pat && a.N == 12)  // the size of BASELINE config 2: N as a compile-time constant
                 return a.red ? launch_sweep<MODE, G, false, 3, true, false, 12>(a, s) : launch_sweep<MODE, G, false, 3, false, false, 12>(a, s);
-#ifndef MCQ_EXP_NO_NC5  // (timing experiment: without these instantiations)
             // the long cells of measure_min_energy_vs_N (BASELINE configs[3]): N as a compile-time constant (125 / 119 / 118 VGPRs and 10 / 7 / 4
             // spilled SGPRs against 128 / 40 of the generic five-pass variant; N = 19 is left out: its instantiation spills 324 VGPRs)
             if (!pat && !a.red && (a.N == 17 || a.N == 18 || a.N == 20)) switch (a.N) {
@@ -2648,7 +2552,6 @@ int launch_sweep_g(const KArgs& a, hipStream_t s) {
                 case 18: return launch_sweep<MODE, G, false, 5, false, false, 18>(a, s);
                 default: return launch_sweep<MODE, G, false, 5, false, false, 20>(a, s);
                 }
-#endif
             if (!pat) switch ((a.N + G - 1) / G) {
 #define MCQ_NT_CASE(nt) case nt: return a.red ? launch_sweep<MODE, G, false, (nt >= 4 ? 0 : nt), true>(a, s) : launch_sweep<MODE, G, false, nt, false>(a, s)
                 MCQ_NT_CASE(1);  // N = 2..4

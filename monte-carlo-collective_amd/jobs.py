@@ -193,12 +193,6 @@ class JobSet:
             shapes = [(self.jobs[groups[k][0]]["N"], len(self.shards[groups[k][0]][0]) * len(groups[k]),
                        abi.mode_of(self.jobs[groups[k][0]]["mcmc_type"])) for k in keys]
             lanes = dict(zip(keys, plan_lanes(shapes, L.mcq_device_simds(), L.mcq_default_lanes_n)))
-            # (experiments only, tools/r04_shapes.sh: MCQ_LANES_PLAN="17:8,18:8" overrides the plan for boards of those N)
-            for item in filter(None, os.environ.get("MCQ_LANES_PLAN", "").split(",")):
-                n_, g_ = (int(x) for x in item.split(":"))
-                for k, (N, _, m) in zip(keys, shapes):
-                    if N == n_ and m == abi.MODE_BOARD:
-                        lanes[k] = g_
         for key, ids in groups.items():
             j0 = self.jobs[ids[0]]
             n = len(self.shards[ids[0]][0])
@@ -212,7 +206,7 @@ class JobSet:
                 p = abi.make_params(j0["N"], j0["n_steps"], j0["init_mode"], j0["schedule_params"], n, mcmc_type=j0["mcmc_type"],
                                     early_stop_patience=j0["early_stop_patience"], trace=self.trace, lanes_per_chain=lanes_per_chain, rng=rng)
                 seeds = self.shards[ids[0]][0]
-            run = _lib.DeviceRun(p, seeds, trace=self.trace, states=False, stream_words=os.environ.get("MCQ_JOB_STREAM_WORDS") == "1")  # (experiment hook: the count costs a job list one small kernel per launch)
+            run = _lib.DeviceRun(p, seeds, trace=self.trace, states=False, stream_words=False)  # (the count costs a job list one small kernel per launch: profiles/r04_c4_stream_words_ab.txt)
             la = _Launch(ids, run, n, n)
             self.launches.append(la)  # (its stream: below, once it is known whether the launches get CUs of their own)
         # longest first, by the estimated time of one of its wavefronts: the launches that follow fill in behind it

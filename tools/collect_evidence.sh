@@ -24,8 +24,6 @@ step "stamps" "(tools/stamp_profile.sh 2>&1 | grep STAMP | sed 's/^/board   /'; 
 step "occupancy sweep, N = 24 board (8 lanes, reduced trace)" "for c in 8192 16384 32768 65536 131072; do python bench.py --N 24 --trace reduced --schedule sinusoidal_annealing --lanes 8 --no-states --chains \$c --n-steps 20000 --steps 2 --no-cpu-baseline | python -c \"import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('N=24 board chains', \$c, 'moves/s %.4e' % d['value'], 'sweep_ms %.2f' % d['kernel_ms']['sweep'])\"; done | tee $OUT/occupancy_n24.txt"
 step "config 4 at SURVEY 8d's 10^6 steps (8 192 chains per cell, no trace)" "python bench.py --config c4 --chains 8192 --n-steps 1000000 --steps 1 --warmup 0 --no-cpu-baseline | $J | tee $OUT/c4_1e6.json | cut -c1-300"
 step "small launches vs hardware queues" "for q in 4 8 16 24 32; do GPU_MAX_HW_QUEUES=\$q python bench.py --config c4 --no-cpu-baseline --steps 2 | python -c \"import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('c4 1024 chains/cell, GPU_MAX_HW_QUEUES', \$q, 'moves/s %.4e' % d['value'], d['kernel_ms'], 'launches', d['config']['launches_per_rank'])\"; done | tee $OUT/small_launches.txt"
-step "LDS stride A/B (same-offset accesses of the 8 chains of an access group: stride 4 mod 8 words vs 0 mod 8)" "ROUNDS=2 tools/ab.sh '--steps 2 --warmup 1' shipped build/libmcq_hip_stride0.so | tee $OUT/lds_stride_ab.txt"
-step "LDS conflict counters for both strides" "tools/lds_stride_pmc.sh $OUT | tee $OUT/lds_stride_pmc.txt"
 step "c5 host memory" "python -c \"
 import resource, subprocess, sys
 p = subprocess.run([sys.executable, 'bench.py', '--config', 'c5', '--chains', '8192', '--steps', '1', '--no-cpu-baseline'], capture_output=True, text=True)
