@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MCQ_ABI_VERSION 5
+#define MCQ_ABI_VERSION 6
 
 /* error codes */
 #define MCQ_OK 0
@@ -298,6 +298,68 @@ int mcq_beta_table_device(const mcq_params* p, double* beta_out, float* c32_out,
  */
 int mcq_run_host(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out,
                  double* kernel_seconds);
+
+/*
+ * Chains that go on where an earlier call left them (ABI 6).  mcq_run_device and mcq_run_host are one shot: seed, build the initial state,
+ * sweep n_steps.  The *_from calls run steps [first_step, first_step + p->n_steps) of a schedule of schedule_steps steps, from the initial
+ * state (a first segment) or from given placements and MT19937 states; mcq_checkpoint_device hands the streams back.  Run [0, K) with
+ * state = NULL, checkpoint, run [K, T) from the checkpoint (state = the first call's final_state, stream = the checkpoint's states): the
+ * two energy histories (entry 0 of the second repeats the last entry of the first), accept bits, final state and stream equal those of ONE
+ * mcq_run_device with n_steps = T word for word, for any K and any number of cuts.
+ *   - beta of step s of the call is beta(first_step + s) of the schedule_steps-long schedule.  A p->beta_table covers THIS call's n_steps
+ *     (the caller slices the whole table); without one the device evaluates the schedule with the offset and the whole length.
+ *   - every output is relative to the call: initial_energy (recounted from the given state, so it can be checked against the final_energy
+ *     of the call before), best_energy, steps_to_best, n_accepted, stream_words, the step_* arrays of the reduced trace.  Merging the
+ *     segments is host work (monte-carlo-collective_amd/checkpoint.py).
+ *   - with `state` given, p->init and sets[].init_plus1 are ignored and no initialisation draw is taken.
+ *   - schedule sets, every trace mode, lane count and size mcq_run_device serves are served.
+ * MCQ_EINVAL (mcq_validate_resume tells without a device): first_step < 0 or first_step + n_steps > schedule_steps; exchange_every > 0 (the
+ * rungs are not part of a checkpoint); a board patience that could trigger, 0 <= patience <= schedule_steps (the no-improvement counter is
+ * not carried); rng = PHILOX with `stream` or `state`; `stream` without `state` (a first segment that continues a stream takes
+ * p->stream_states); `state` with p->stream_states; a `state` that is not 16-byte aligned.
+ * NOT checked, the data being on the device -- it is made harmless instead: a position above 624 in `stream` reads as 624, and every byte of
+ * `state` is clamped to N - 1 (a board height or a full_3d coordinate beyond the board); two queens of a full_3d state on one cell share a
+ * column bit, so the energies of such a chain mean nothing, and nothing outside the chain's own tables is touched.
+ * `state` may be out->final_state of the same call (the usual chain of segments): the placements are read by the kernel that takes the
+ * init kernel's place, which has finished before the sweep writes final_state.
+ * A `stream` at position 0 (NumPy never stands there by itself: only set_state() puts it there) is continued like any other, but the low
+ * 31 bits of key word 0 that a checkpoint hands back BEFORE the chain has drawn its first generation are not the caller's: no twist ever
+ * reads those bits, so every draw is the same; only the comparison of that one key word with the caller's copy is not.
+ */
+typedef struct mcq_resume {
+    int64_t first_step;     /* index, in the WHOLE schedule, of this call's step 0 */
+    int64_t schedule_steps; /* length of the whole schedule; the call runs steps [first_step, first_step + p->n_steps) of it */
+    const uint8_t* state;   /* [n_chains][state_bytes], final_state layout, 16-byte aligned; NULL = build the initial state as mcq_run_device does
+                               (first segment) */
+    const uint32_t* stream; /* [n_chains][625] MT19937 states exactly as np.random.get_state() holds them (624 key words, position); NULL = seed
+                               from seeds[r] (np.random.seed), taking no initialisation draws when `state` is given */
+} mcq_resume;
+
+/* the MCQ_EINVAL conditions above, pure host code: MCQ_OK or MCQ_EINVAL with mcq_last_error() */
+int mcq_validate_resume(const mcq_params* p, const mcq_resume* from);
+
+/* mcq_run_device for a segment: `from->state` / `from->stream` are DEVICE pointers, read by a kernel that takes the init kernel's place
+ * (no host staging, no synchronise); asynchronous like mcq_run_device, same workspace (mcq_workspace_bytes(p)). */
+int mcq_run_device_from(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out,
+                        void* workspace, size_t workspace_bytes, void* hip_stream);
+/* ... with the events of mcq_run_device_timed: init_ms is the restore kernel's time when `from->state` is given.  Blocking. */
+int mcq_run_device_from_timed(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
+                              size_t workspace_bytes, void* hip_stream, float* init_ms, float* sweep_ms);
+
+/* Enqueued behind a run (mcq_run_device or mcq_run_device_from, MCQ_RNG_MT19937_NUMPY) on the same stream, with that run's parameters and
+ * workspace: turns what the sweep left in the workspace into the MT19937 state NumPy itself would hold after as many draws -- one
+ * generation, position 1 .. 624 (a chain that has consumed a whole generation reports 624, never 0) -- into `stream_out`, DEVICE
+ * uint32[n_chains][625].  The placement half of a checkpoint is out->final_state of the run.  The workspace must not have been used in
+ * between.  After a plain mcq_run_device the stream is where the chain left it, whatever made it leave: a board chain that stopped early
+ * (patience) stands behind the words of its last executed step, and with replica exchange the exchange uniforms are counted like every
+ * other word -- in both cases NumPy's state after out->stream_words words (such a run cannot be CONTINUED: mcq_validate_resume).  MCQ_EINVAL: rng = PHILOX; p->n_steps above 2^28 (the workspace counts the words of the segment in 32 bits).  Asynchronous. */
+int mcq_checkpoint_device(const mcq_params* p, const mcq_outputs* out, void* workspace, size_t workspace_bytes, uint32_t* stream_out,
+                          void* hip_stream);
+
+/* mcq_run_host for a segment: `from->state`, `from->stream` and `stream_out` (optional: the checkpoint's states, uint32[n_chains][625])
+ * are HOST buffers.  Blocking. */
+int mcq_run_host_from(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, uint32_t* stream_out,
+                      double* kernel_seconds);
 
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 

@@ -160,6 +160,17 @@ def lib():
         L.mcq_beta_table_device.argtypes = [C.POINTER(abi.Params), C.c_void_p, C.c_void_p, C.c_void_p]
         L.mcq_run_host.restype = C.c_int
         L.mcq_run_host.argtypes = [C.POINTER(abi.Params), C.c_void_p, C.POINTER(abi.Outputs), C.POINTER(C.c_double)]
+        L.mcq_validate_resume.restype = C.c_int
+        L.mcq_validate_resume.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Resume)]
+        L.mcq_run_device_from.restype = C.c_int
+        L.mcq_run_device_from.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Resume), C.c_void_p, C.POINTER(abi.Outputs), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mcq_run_device_from_timed.restype = C.c_int
+        L.mcq_run_device_from_timed.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Resume), C.c_void_p, C.POINTER(abi.Outputs), C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.mcq_checkpoint_device.restype = C.c_int
+        L.mcq_checkpoint_device.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Outputs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.mcq_run_host_from.restype = C.c_int
+        L.mcq_run_host_from.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Resume), C.c_void_p, C.POINTER(abi.Outputs), C.c_void_p, C.POINTER(C.c_double)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -226,14 +237,49 @@ def run_host(params, seeds, trace=True, states=True):
     return arrays, secs.value
 
 
+def validate_resume(params, resume):
+    """mcq_validate_resume: raises ValueError for a segment the library does not run (pure host code, no GPU needed)."""
+    _check(lib().mcq_validate_resume(C.byref(params), C.byref(resume)))
+
+
+def run_host_from(params, seeds, resume, checkpoint=True, trace=True, states=True):
+    """One segment of a longer run with NumPy (host) buffers (mcq_run_host_from): `resume` is an abi.Resume (abi.make_resume) that names
+    the segment's place in the whole schedule and, for a continued chain, the placements and MT19937 states it starts from.  beta comes
+    from the WHOLE schedule's table (abi.segment_beta_table).  With checkpoint=True the result holds `stream_state`, uint32[n_chains][625]:
+    the MT19937 states as np.random.get_state() would hold them after the segment.  Returns ({field: ndarray}, kernel_seconds)."""
+    L = lib()
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    if seeds.shape != (params.n_chains,):
+        raise ValueError("seeds must have one entry per chain")
+    p = abi.copy_params(params)
+    p.trace = abi.trace_mode(trace)
+    _check(L.mcq_validate_resume(C.byref(p), C.byref(resume)))
+    tab = abi.segment_beta_table(p, resume.first_step, resume.schedule_steps) if not p.beta_table else None
+    if tab is not None:
+        p.beta_table = tab.ctypes.data
+    arrays = {k: np.zeros(shape, dtype=abi.OUTPUT_DTYPES[k])
+              for k, shape in abi.output_shapes(p, trace=trace, states=states).items()}
+    out = abi.Outputs()
+    for k, a in arrays.items():
+        setattr(out, k, a.ctypes.data)
+    ss = np.zeros((int(p.n_chains), 625), dtype=np.uint32) if checkpoint else None
+    secs = C.c_double(0.0)
+    _check(L.mcq_run_host_from(C.byref(p), C.byref(resume), seeds.ctypes.data, C.byref(out), ss.ctypes.data if checkpoint else None, C.byref(secs)))
+    if checkpoint:
+        arrays["stream_state"] = ss
+    return arrays, secs.value
+
+
 class DeviceRun:
     """Device-resident buffers for repeated launches (bench.py, multi-GPU driver).
 
     torch is used only as the allocator / stream provider; the kernels are launched by
     libmcq_hip.so through raw device pointers."""
 
-    def __init__(self, params, seeds, trace=True, states=True, device=None, stream_words=True):
-        """stream_words=False leaves mcq_outputs.stream_words NULL (a job list has no use for it: one small kernel less per launch)."""
+    def __init__(self, params, seeds, trace=True, states=True, device=None, stream_words=True, schedule_steps=None):
+        """stream_words=False leaves mcq_outputs.stream_words NULL (a job list has no use for it: one small kernel less per launch).
+        schedule_steps: the launches are segments of `params.n_steps` steps of a schedule of that many (launch_from): the beta table of the
+        WHOLE schedule is kept on the device and each launch reads its slice."""
         import torch
 
         self.torch = torch
@@ -254,7 +300,15 @@ class DeviceRun:
             if s.shape != (self.p.n_chains,):
                 raise ValueError("seeds must have one entry per chain")
             self.seeds = torch.from_numpy(s.view(np.int32).copy()).to(self.device)
-            tab = abi.host_beta_table(self.p) if not self.p.beta_table else None  # beta as the reference's own NumPy arithmetic gives it
+            self.schedule_steps = None if schedule_steps is None else int(schedule_steps)
+            if self.schedule_steps is None:
+                tab = abi.host_beta_table(self.p) if not self.p.beta_table else None  # beta as the reference's own NumPy arithmetic gives it
+            else:
+                tab = abi.segment_beta_table(self.p, 0, self.schedule_steps) if self.schedule_steps == self.p.n_steps else None
+                whole = abi.copy_params(self.p)
+                whole.n_steps = self.schedule_steps
+                wt = abi.host_beta_table(whole)
+                self.beta_whole = None if wt is None else torch.from_numpy(wt).to(self.device)  # [n_sets][schedule_steps]
             if tab is not None:
                 self.beta = torch.from_numpy(tab).to(self.device)
                 self.p.beta_table = self.beta.data_ptr()
@@ -270,6 +324,46 @@ class DeviceRun:
         with torch.cuda.device(self.device):
             _check(self.L.mcq_run_device(C.byref(self.p), self.seeds.data_ptr(), C.byref(self.out),
                                          self.ws.data_ptr(), self.ws_bytes, C.c_void_p(st.cuda_stream)))
+
+    def launch_from(self, first_step, state=None, stream_state=None, stream=None, timed=False):
+        """Enqueue one segment (mcq_run_device_from): steps [first_step, first_step + n_steps) of the schedule of `schedule_steps` steps given
+        to the constructor, from `state` (uint8 tensor [n_chains][state_bytes] on the device, e.g. self.t["final_state"] of the segment before;
+        None: the initial state) and `stream_state` (int32 tensor [n_chains][625], what checkpoint() filled; None: seeded).  Nothing is copied
+        to the host; asynchronous unless timed=True, which returns (restore or init ms, sweep ms)."""
+        torch = self.torch
+        if self.schedule_steps is None:
+            raise ValueError("launch_from needs a DeviceRun built with schedule_steps")
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        r = abi.Resume()
+        r.first_step, r.schedule_steps = int(first_step), self.schedule_steps
+        r.state = None if state is None else state.data_ptr()
+        r.stream = None if stream_state is None else stream_state.data_ptr()
+        p = abi.copy_params(self.p)
+        n = int(p.n_steps)
+        with torch.cuda.device(self.device), torch.cuda.stream(st):
+            if self.beta_whole is not None and n > 0:
+                self._beta_seg = self.beta_whole[:, int(first_step): int(first_step) + n].contiguous()  # (kept until the next launch)
+                p.beta_table = self._beta_seg.data_ptr()
+            if timed:
+                i_ms, s_ms = C.c_float(0), C.c_float(0)
+                _check(self.L.mcq_run_device_from_timed(C.byref(p), C.byref(r), self.seeds.data_ptr(), C.byref(self.out), self.ws.data_ptr(),
+                                                        self.ws_bytes, C.c_void_p(st.cuda_stream), C.byref(i_ms), C.byref(s_ms)))
+                return i_ms.value, s_ms.value
+            _check(self.L.mcq_run_device_from(C.byref(p), C.byref(r), self.seeds.data_ptr(), C.byref(self.out), self.ws.data_ptr(),
+                                              self.ws_bytes, C.c_void_p(st.cuda_stream)))
+
+    def checkpoint(self, stream_state=None, stream=None):
+        """Enqueue mcq_checkpoint_device behind the last launch on the same stream: the chains' MT19937 states as NumPy would hold them, into
+        `stream_state` (int32 tensor [n_chains][625] on the device; allocated when None).  The placements are self.t["final_state"].  Returns
+        the tensor; asynchronous."""
+        torch = self.torch
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
+        with torch.cuda.device(self.device):
+            if stream_state is None:
+                stream_state = torch.empty((int(self.p.n_chains), 625), dtype=torch.int32, device=self.device)
+            _check(self.L.mcq_checkpoint_device(C.byref(self.p), C.byref(self.out), self.ws.data_ptr(), self.ws_bytes, stream_state.data_ptr(),
+                                                C.c_void_p(st.cuda_stream)))
+        return stream_state
 
     def launch_timed(self, stream=None):
         """Like launch(), but brackets the init and sweep kernels with HIP events recorded on the launch

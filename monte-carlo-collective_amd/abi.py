@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 OK, EINVAL, EDEVICE, ENOMEM = 0, -1, -2, -3
 
@@ -80,6 +80,16 @@ class Params(C.Structure):
         ("n_queens", C.c_int32),
         ("exchange_ladder", C.POINTER(C.c_double)),
         ("stream_states", C.c_void_p),
+    ]
+
+
+class Resume(C.Structure):
+    """include/mcq.h: mcq_resume -- the segment of a longer schedule a call runs, and what it starts from"""
+    _fields_ = [
+        ("first_step", C.c_int64),
+        ("schedule_steps", C.c_int64),
+        ("state", C.c_void_p),
+        ("stream", C.c_void_p),
     ]
 
 
@@ -414,3 +424,45 @@ def set_exchange(params, every, ladder):
     params.exchange_ladder = lad.ctypes.data_as(C.POINTER(C.c_double))
     params._ladder_keepalive = lad
     return params
+
+
+def make_resume(params, first_step, schedule_steps, state=None, stream_state=None):
+    """A Resume block for a call with `params` (host buffers: _lib.run_host_from): steps [first_step, first_step + n_steps) of a
+    schedule of `schedule_steps` steps, from `state` (uint8[n_chains][state_bytes], the final_state layout; None: the initial
+    state) and `stream_state` (uint32[n_chains][625], np.random.get_state() key words + position; None: seeded)."""
+    r = Resume()
+    r.first_step, r.schedule_steps = int(first_step), int(schedule_steps)
+    n, sb = int(params.n_chains), state_bytes(params.N, params.mode, params.n_queens)
+    if state is not None:
+        st = np.ascontiguousarray(state, dtype=np.uint8)
+        if st.shape != (n, sb):
+            raise ValueError(f"state must be uint8[{n}][{sb}] for these parameters, got {st.shape}")
+        if st.ctypes.data % 16:  # rows are read 16 bytes at a time
+            buf = np.zeros(st.size + 16, dtype=np.uint8)
+            off = (-buf.ctypes.data) % 16
+            al = buf[off: off + st.size].reshape(st.shape)
+            al[...] = st
+            st = al
+            r._state_base = buf
+        r.state = st.ctypes.data
+        r._state_keepalive = st
+    if stream_state is not None:
+        ss = np.ascontiguousarray(stream_state, dtype=np.uint32)
+        if ss.shape != (n, 625):
+            raise ValueError("one MT19937 state (624 key words + position) per chain")
+        r.stream = ss.ctypes.data
+        r._stream_keepalive = ss
+    return r
+
+
+def segment_beta_table(params, first_step, schedule_steps):
+    """float64 [n_sets][n_steps]: entries [first_step, first_step + n_steps) of the beta table of the WHOLE schedule of
+    `schedule_steps` steps -- the reference's own arithmetic on the whole run (beta_values), sliced, so a run in segments gets the
+    values the unbroken run gets.  None when the schedules are not known on the Python side (host_beta_table)."""
+    if not getattr(params, "_schedules", None) or params.n_steps <= 0:
+        return None
+    whole = copy_params(params)
+    whole.n_steps = int(schedule_steps)
+    tab = host_beta_table(whole)
+    a = int(first_step)
+    return np.ascontiguousarray(tab[:, a: a + int(params.n_steps)])

@@ -6,8 +6,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(CSRC, "libmcq_hip.so")
-SOURCES = [os.path.join(CSRC, "mcq_hip.hip")]
-HEADER = os.path.join(os.path.dirname(HERE), "include", "mcq.h")
+SOURCES = [os.path.join(CSRC, "mcq_hip.hip"), os.path.join(CSRC, "mcq_resume.hip")]  # the sweep and its C-ABI; the restore / checkpoint kernels
+HEADERS = [os.path.join(os.path.dirname(HERE), "include", "mcq.h"), os.path.join(CSRC, "mcq_record.h")]
+HEADER = HEADERS[0]
 # -ffp-contract=off: the reference's schedule / acceptance expressions are evaluated without
 # fused multiply-adds (hipcc's default would contract beta_start + frac * delta into an FMA).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-fPIC", "-shared"]
@@ -24,7 +25,7 @@ def stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    return any(os.path.getmtime(f) > t for f in SOURCES + [HEADER])
+    return any(os.path.getmtime(f) > t for f in SOURCES + HEADERS)
 
 
 def build(force=False, verbose=False):

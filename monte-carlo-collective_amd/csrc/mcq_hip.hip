@@ -64,6 +64,7 @@
 #include <vector>
 
 #include "../../include/mcq.h"
+#include "mcq_record.h"
 
 extern "C" int32_t mcq_default_lanes(int32_t mode);
 extern "C" int32_t mcq_default_lanes_n(int32_t mode, int32_t N);
@@ -111,16 +112,10 @@ namespace {
 #define STAMP_COUNT(k)
 #endif
 
-constexpr int MT_N = 624;
-constexpr int MT_M = 397;
 constexpr int RING = 64;          // ready (tempered) words per chain
 constexpr int RING_MIRROR = 32;   // slots 0..31 are repeated behind the ring: a proposal reads up to 31 slots past pos without wrapping
 constexpr int RED_STRIPES = 8;    // trace == REDUCED: independent accumulator copies, so one address sees few atomics
-constexpr int REC_MIRROR = 624;   // record word: copy of MT word 0, so that words i+1 and i+397.. of a block never wrap inside a lane's run
-constexpr int REC_POS = 625;      // record word: MT index of the next word to consume
-constexpr int REC_GEN_END = 626;  // record word: words [0, gen_end) belong to the current generation
-constexpr int REC_E0 = 627;       // record word: initial energy
-constexpr int REC_STATE = 628;    // first word of the state bytes (heights or (i,j,k) triplets)
+// (MT_N, MT_M and the words of a chain record, REC_*: csrc/mcq_record.h)
 
 struct KArgs {
     int N, Q, mode, init, sched, rng;  // Q queens: N * N, or mcq_params.n_queens (full_3d, random init)
@@ -157,6 +152,7 @@ struct KArgs {
     uint32_t* perm;           // full_3d beyond N = 32, random init: the N^3 cells np.random.choice permutes, one slice per chain of an init launch (workspace)
     long long chain0;         // init kernel: first chain of this launch (the launches of one run share the `perm` slices)
     const uint32_t* stream;   // mcq_params.stream_states in the layout the kernels stream from, [n_chains][626]: MT words, position, words of the current generation (workspace)
+    long long step0, sched_steps;  // mcq_beta_kernel: table entry s is beta(step0 + s) of a schedule of sched_steps steps (mcq_resume: a segment of a longer run; else 0 and n_steps)
 };
 
 __device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
@@ -255,7 +251,7 @@ struct InitRng {
 // experiments.py:13-77, evaluation order kept, float64, no contraction.
 __device__ double beta_at(const KArgs& a, long long step) {
     const double bs = a.beta_start, be = a.beta_end;
-    const long long n = a.n_steps;
+    const long long n = a.sched_steps;
     switch (a.sched) {
     case MCQ_SCHED_CONSTANT:
         return a.beta_const;
@@ -289,7 +285,7 @@ __device__ double beta_at(const KArgs& a, long long step) {
 __global__ __launch_bounds__(256) void mcq_beta_kernel(KArgs a) {
     const long long s = (long long)blockIdx.x * 256 + threadIdx.x;
     if (s < a.n_steps) {
-        const double b = beta_at(a, s);
+        const double b = beta_at(a, a.step0 + s);
         a.beta_tab[s] = b;
         if (a.c32_tab) a.c32_tab[s] = (float)(-b * 1.4426950408889634);
     }
@@ -492,58 +488,9 @@ __global__ __launch_bounds__(64) void mcq_init_kernel(KArgs a) {
         }
     }
 
-    // E0 = number of unordered attacking pairs (mcmc_board.py:82-122, mcmc.py:134-169).  Two distinct cells attack iff they
-    // share one of the 13 lines through a cell, and no two cells share more than one, so E0 = sum over lines of c (c - 1) / 2
-    // with c the queens on the line: one byte counter per line (c <= N), O(Q) increments instead of Q^2 / 2 pair tests.
-    //   N^2 lines each:        (j, k) along i | (i, k) along j | (i, j) along k
-    //   N (2N - 1) lines each: (k, i - j), (k, i + j) | (j, i - k), (j, i + k) | (i, j - k), (i, j + k)      planar diagonals
-    //   (2N - 1)^2 lines each: (i - j, i - k), (i - j, i + k), (i + j, i - k), (i + j, i + k)                space diagonals
-    // One family at a time in a (2N - 1)^2-byte array that takes the place of the permutation array (no longer needed): all 13
-    // at once are 30 N^2 bytes, which keeps a CU to few chains at N = 12 and does not fit at all beyond N = 70.
-    int e = 0;
-    {
-        uint32_t* cnt = (uint32_t*)perm;
-        const int D = 2 * N - 1, o = N - 1;
-        const bool board = a.mode == MCQ_MODE_BOARD;
-        for (int f = 0; f < 13; f++) {
-            if (f == 2 && board) continue;  // lines along k: on a board the column (i, j) itself, one queen each
-            const int lines = f < 3 ? N * N : f < 9 ? N * D : D * D;
-            for (int w = sub; w < (lines + 3) / 4; w += L) cnt[w] = 0;
-            __syncthreads();  // (a workgroup of one wavefront: orders the phases for the compiler as well)
-            for (int c = sub; c < Q; c += L) {
-                int i, j, k;
-                if (board) i = c / N, j = c % N, k = st[c];
-                else i = st[3 * c], j = st[3 * c + 1], k = st[3 * c + 2];
-                int line;
-                switch (f) {
-                case 0: line = j * N + k; break;
-                case 1: line = i * N + k; break;
-                case 2: line = i * N + j; break;
-                case 3: line = k * D + (i - j + o); break;
-                case 4: line = k * D + (i + j); break;
-                case 5: line = j * D + (i - k + o); break;
-                case 6: line = j * D + (i + k); break;
-                case 7: line = i * D + (j - k + o); break;
-                case 8: line = i * D + (j + k); break;
-                case 9: line = (i - j + o) * D + (i - k + o); break;
-                case 10: line = (i - j + o) * D + (i + k); break;
-                case 11: line = (i + j) * D + (i - k + o); break;
-                default: line = (i + j) * D + (i + k); break;
-                }
-                atomicAdd(&cnt[line >> 2], 1u << (8 * (line & 3)));
-            }
-            __syncthreads();
-            for (int w = sub; w < (lines + 3) / 4; w += L) {
-                const uint32_t x = cnt[w];
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const int c = (int)((x >> (8 * b)) & 0xffu);
-                    e += c * (c - 1) / 2;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    // E0 = number of unordered attacking pairs, from one byte counter per line, one family of lines at a time in a (2N - 1)^2-byte array that
+    // takes the place of the permutation array (no longer needed): mcq_count_e0, csrc/mcq_record.h
+    int e = mcq_count_e0(st, (uint32_t*)perm, N, Q, a.mode == MCQ_MODE_BOARD, sub, L);
     e = group_sum(e);
 
     if (!valid) return;
@@ -820,7 +767,10 @@ struct Stream {
 #pragma unroll
             for (int w = 0; w < WPL; w++) bitsq |= ((t[w] & maskQ) <= mQ ? 1u : 0u) << (gl * WPL + w);
         }
-        if (i0 == 0) *word(REC_MIRROR) = v[0];
+        if (i0 == 0) {  // (the old word 0 goes to REC_OLD0, through the mirror's address: its low bits go into no later word, and mcq_checkpoint_kernel needs them)
+            uint32_t* const m = word(REC_MIRROR);
+            m[0] = v[0], m[REC_OLD0 - REC_MIRROR] = pa[0];
+        }
         if (HASQ) {  // both 16-bit masks through one reduction over the group
             const uint32_t both = group_or<G>(bits | (bitsq << 16));
             add_flags(both & 0xffffu, both >> 16);
@@ -1988,7 +1938,11 @@ __global__ __launch_bounds__(64, G == 2 ? 2 : (MODE == MCQ_MODE_FULL3D && G == 4
             // kernel wrote the words IT took and mcq_stream_words_kernel adds this position minus the one the sweep started from.  (Through the stream's own
             // base + offset registers: a store to a.out.stream_words here would keep three more kernel arguments alive across the loop -- 2 VGPRs and 3-17
             // spilled SGPRs more in every variant.)
-            if constexpr (!PHILOX) *rng.word(REC_GEN_END) = rng.pos;  // (a Philox stream is addressed by position, there is nothing to hand back: stream_words is 0)
+            // Next to it, for mcq_checkpoint_kernel (csrc/mcq_record.h): where the twist stopped, in the mirror word, which has no reader left.
+            if constexpr (!PHILOX) {  // (a Philox stream is addressed by position, there is nothing to hand back: stream_words is 0)
+                uint32_t* const ge = rng.word(REC_GEN_END);
+                ge[0] = rng.pos, ge[REC_BOUNDARY - REC_GEN_END] = rng.gen;
+            }
             if (EXCH && a.out.exchange_rung) a.out.exchange_rung[chain] = rung;
             if (EXCH && a.out.n_exchanges) a.out.n_exchanges[chain] = n_exch;
         }
@@ -2308,6 +2262,25 @@ int chain_lds_words_for(int N, int mode, bool narrow, int Q = 0, bool slim = fal
     return w;
 }
 
+// mcq_resume (include/mcq.h): what a call that runs a segment of a longer schedule, or starts from given placements, can take
+int validate_resume(const mcq_params* p, const mcq_resume* from) {
+    int rc = validate(p);
+    if (rc != MCQ_OK) return rc;
+    if (!from) return fail(MCQ_EINVAL, "null mcq_resume");
+    if (from->first_step < 0) return fail(MCQ_EINVAL, "resume: first_step must not be negative");
+    if (from->schedule_steps < 0 || from->first_step > from->schedule_steps - p->n_steps)
+        return fail(MCQ_EINVAL, "resume: the segment [first_step, first_step + n_steps) must lie inside the schedule of schedule_steps steps");
+    if (p->exchange_every > 0) return fail(MCQ_EINVAL, "resume: replica exchange cannot be continued (the rungs are not part of a checkpoint)");
+    if (p->mode == MCQ_MODE_BOARD && p->patience >= 0 && p->patience <= from->schedule_steps)
+        return fail(MCQ_EINVAL, "resume: early stopping that could trigger cannot be continued (the no-improvement counter is not part of a checkpoint); pass early_stop_patience None");
+    if (from->stream && p->rng != MCQ_RNG_MT19937_NUMPY) return fail(MCQ_EINVAL, "resume: stream continues an MT19937 stream (a Philox stream is a function of its seed)");
+    if (from->stream && !from->state) return fail(MCQ_EINVAL, "resume: stream without state (a first segment that continues a stream takes mcq_params.stream_states)");
+    if (from->state && p->stream_states) return fail(MCQ_EINVAL, "resume: stream_states applies to a first segment (state NULL); a continued chain takes mcq_resume.stream");
+    if (from->state && p->rng != MCQ_RNG_MT19937_NUMPY) return fail(MCQ_EINVAL, "resume: a Philox chain cannot be continued (its stream position is not part of a checkpoint)");
+    if (((uintptr_t)from->state & 15u) != 0 || ((uintptr_t)from->stream & 3u) != 0) return fail(MCQ_EINVAL, "resume: state must be 16-byte aligned, stream 4-byte aligned");
+    return MCQ_OK;
+}
+
 int build_args(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, void* ws, KArgs* a) {
     memset(a, 0, sizeof *a);
     a->N = p->N, a->Q = queens_of(p), a->NN = p->N * p->N, a->mode = p->mode, a->init = p->init, a->sched = p->sched, a->flags = p->flags, a->rng = p->rng;
@@ -2329,6 +2302,7 @@ int build_args(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* ou
     a->chain_lds_words = chain_lds_words_for(p->N, p->mode, false, a->Q);  // full_3d: the launcher picks the 16-bit layout where it applies
     a->beta_const = p->beta_const, a->beta_start = p->beta_start, a->beta_end = p->beta_end;
     a->n_steps = p->n_steps, a->n_chains = p->n_chains;
+    a->step0 = 0, a->sched_steps = p->n_steps;
     a->patience = p->mode == MCQ_MODE_BOARD ? p->patience : -1;  // full_3d ignores early_stop_patience (experiments.py:199-279)
     a->hist_stride = p->hist_stride, a->bits_stride = p->bits_stride;
     a->beta_tab = (double*)ws;
@@ -2607,8 +2581,8 @@ int launch_sweep_mode(const KArgs& a, int G, hipStream_t s) {
 }
 
 int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
-                    size_t workspace_bytes, void* hip_stream, hipEvent_t* ev, const double* beta_table_dev) {
-    int rc = validate(p);
+                    size_t workspace_bytes, void* hip_stream, hipEvent_t* ev, const double* beta_table_dev, const mcq_resume* from = nullptr) {
+    int rc = from ? validate_resume(p, from) : validate(p);
     if (rc != MCQ_OK) return rc;
     if (!seeds || !out || !workspace) return fail(MCQ_EINVAL, "null argument");
     if (workspace_bytes < mcq_workspace_bytes(p)) return fail(MCQ_ENOMEM, "workspace too small");
@@ -2638,6 +2612,7 @@ int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_output
     KArgs a;
     rc = build_args(p, seeds, out, workspace, &a);
     if (rc != MCQ_OK) return rc;
+    if (from) a.step0 = from->first_step, a.sched_steps = from->schedule_steps;  // (a beta_table covers this call's steps only)
 
     const int G = effective_lanes(p);
     {  // the variant this launch takes must fit the LDS: found out before anything is enqueued
@@ -2735,7 +2710,14 @@ int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_output
                 hipLaunchKernelGGL(mcq_beta_kernel, dim3((unsigned)((p->n_steps + 255) / 256)), dim3(256), 0, s, b);
         }
     }
-    {  // sets may start from different init modes (one launch of the init kernel per distinct run of sets)
+    if (from && from->state) {  // the caller's placements and streams instead of an initial state (init and sets[].init_plus1 do not apply)
+        McqRestoreArgs r;
+        memset(&r, 0, sizeof r);
+        r.N = a.N, r.Q = a.Q, r.mode = a.mode, r.state_bytes = a.state_bytes, r.rec_words = a.rec_words, r.n_chains = a.n_chains;
+        r.ws = a.ws, r.state = from->state, r.stream = from->stream, r.seeds = a.seeds, r.qtab = a.qtab, r.qtab_stride = a.qtab_stride;
+        r.initial_energy = a.out.initial_energy, r.stream_words = a.out.stream_words;
+        HIP_TRY(mcq_launch_restore(r, s));
+    } else {  // sets may start from different init modes (one launch of the init kernel per distinct run of sets)
         bool mixed = false;
         for (size_t t = 0; t < n_sets_of(p) && p->n_sets > 1; t++) mixed |= p->sets[t].init_plus1 != 0;
         if (!mixed) {
@@ -2826,8 +2808,8 @@ int mcq_run_device(const mcq_params* p, const uint32_t* seeds, const mcq_outputs
     return run_device_impl(p, seeds, out, workspace, workspace_bytes, hip_stream, nullptr, p ? p->beta_table : nullptr);
 }
 
-int mcq_run_device_timed(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
-                         size_t workspace_bytes, void* hip_stream, float* init_ms, float* sweep_ms) {
+static int run_device_timed_impl(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
+                                 size_t workspace_bytes, void* hip_stream, float* init_ms, float* sweep_ms) {
     struct Events {  // destroyed on every return path
         hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
         ~Events() {
@@ -2846,7 +2828,7 @@ int mcq_run_device_timed(const mcq_params* p, const uint32_t* seeds, const mcq_o
     if (!g_dbg) HIP_TRY(hipMalloc((void**)&g_dbg, wt_waves * 32));
     HIP_TRY(hipMemset(g_dbg, 0, wt_waves * 32));
 #endif
-    int rc = run_device_impl(p, seeds, out, workspace, workspace_bytes, hip_stream, ev, p ? p->beta_table : nullptr);
+    int rc = run_device_impl(p, seeds, out, workspace, workspace_bytes, hip_stream, ev, p ? p->beta_table : nullptr, from);
 #ifdef MCQ_STAMPS
     if (rc == MCQ_OK) {
         unsigned long long h[12];
@@ -2895,6 +2877,45 @@ int mcq_run_device_timed(const mcq_params* p, const uint32_t* seeds, const mcq_o
     if (init_ms) *init_ms = a;
     if (sweep_ms) *sweep_ms = b;
     return rc;
+}
+
+int mcq_run_device_timed(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
+                         size_t workspace_bytes, void* hip_stream, float* init_ms, float* sweep_ms) {
+    return run_device_timed_impl(p, nullptr, seeds, out, workspace, workspace_bytes, hip_stream, init_ms, sweep_ms);
+}
+
+int mcq_validate_resume(const mcq_params* p, const mcq_resume* from) { return validate_resume(p, from); }
+
+int mcq_run_device_from(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
+                        size_t workspace_bytes, void* hip_stream) {
+    if (!from) return fail(MCQ_EINVAL, "null mcq_resume");
+    return run_device_impl(p, seeds, out, workspace, workspace_bytes, hip_stream, nullptr, p ? p->beta_table : nullptr, from);
+}
+
+int mcq_run_device_from_timed(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
+                              size_t workspace_bytes, void* hip_stream, float* init_ms, float* sweep_ms) {
+    if (!from) return fail(MCQ_EINVAL, "null mcq_resume");
+    return run_device_timed_impl(p, from, seeds, out, workspace, workspace_bytes, hip_stream, init_ms, sweep_ms);
+}
+
+int mcq_checkpoint_device(const mcq_params* p, const mcq_outputs* out, void* workspace, size_t workspace_bytes, uint32_t* stream_out, void* hip_stream) {
+    (void)out;
+    int rc = validate(p);
+    if (rc != MCQ_OK) return rc;
+    if (p->rng != MCQ_RNG_MT19937_NUMPY) return fail(MCQ_EINVAL, "checkpoint: a Philox stream is a function of its seed and position, there is no state to hand back");
+    if (!workspace || !stream_out) return fail(MCQ_EINVAL, "null argument");
+    // (the record counts the words of the segment in 32 bits; a step takes fewer than 10 on average whatever N)
+    if (p->n_steps > (1LL << 28)) return fail(MCQ_EINVAL, "checkpoint: a segment that is to be checkpointed runs at most 2^28 steps");
+    if (workspace_bytes < mcq_workspace_bytes(p)) return fail(MCQ_ENOMEM, "workspace too small");
+    if (((uintptr_t)workspace & 63u) != 0 || ((uintptr_t)stream_out & 3u) != 0) return fail(MCQ_EINVAL, "workspace must be 64-byte aligned, stream_out 4-byte aligned");
+    if (p->n_chains == 0) return MCQ_OK;
+    KArgs a;
+    mcq_outputs none;
+    memset(&none, 0, sizeof none);
+    rc = build_args(p, nullptr, &none, workspace, &a);  // (for the place of the chain records in the workspace)
+    if (rc != MCQ_OK) return rc;
+    HIP_TRY(mcq_launch_checkpoint(a.ws, a.rec_words, (long long)p->n_chains, stream_out, (hipStream_t)hip_stream));
+    return MCQ_OK;
 }
 
 int mcq_trace_stats_device(const mcq_params* p, const mcq_outputs* out, int64_t* step_sum, int64_t* step_sumsq, int64_t* step_count,
@@ -2968,7 +2989,7 @@ int mcq_beta_table_device(const mcq_params* p, double* beta_out, float* c32_out,
     hipStream_t s = (hipStream_t)hip_stream;
     KArgs a;
     memset(&a, 0, sizeof a);
-    a.n_steps = p->n_steps;
+    a.n_steps = a.sched_steps = p->n_steps;
     for (size_t t = 0; t < n_sets_of(p); t++) {
         if (p->n_sets > 1) a.sched = p->sets[t].sched, a.beta_const = p->sets[t].beta_const, a.beta_start = p->sets[t].beta_start, a.beta_end = p->sets[t].beta_end;
         else a.sched = p->sched, a.beta_const = p->beta_const, a.beta_start = p->beta_start, a.beta_end = p->beta_end;
@@ -2980,10 +3001,11 @@ int mcq_beta_table_device(const mcq_params* p, double* beta_out, float* c32_out,
     return MCQ_OK;
 }
 
-int mcq_run_host(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, double* kernel_seconds) {
-    int rc = validate(p);
+static int run_host_impl(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, uint32_t* stream_out, double* kernel_seconds) {
+    int rc = from ? validate_resume(p, from) : validate(p);
     if (rc != MCQ_OK) return rc;
     if (!seeds || !out) return fail(MCQ_EINVAL, "null argument");
+    if (stream_out && p->rng != MCQ_RNG_MT19937_NUMPY) return fail(MCQ_EINVAL, "checkpoint: a Philox stream is a function of its seed and position, there is no state to hand back");
     if (p->device >= 0) HIP_TRY(hipSetDevice(p->device));
     if (kernel_seconds) *kernel_seconds = 0.0;
     if (p->n_chains == 0) return MCQ_OK;
@@ -3021,10 +3043,15 @@ int mcq_run_host(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* 
     uint32_t* d_seeds = nullptr;
     void* d_ws = nullptr;
     double* d_beta = nullptr;
+    uint8_t* d_state = nullptr;                           // mcq_resume.state / .stream on the device, and the checkpoint's states
+    uint32_t *d_stream = nullptr, *d_stream_out = nullptr;
     const size_t ws_bytes = mcq_workspace_bytes(p);
     auto cleanup = [&]() {
         for (auto& b : bufs)
             if (*b.dev) (void)hipFree(*b.dev);
+        if (d_state) (void)hipFree(d_state);
+        if (d_stream) (void)hipFree(d_stream);
+        if (d_stream_out) (void)hipFree(d_stream_out);
         if (d_seeds) (void)hipFree(d_seeds);
         if (d_ws) (void)hipFree(d_ws);
         if (d_beta) (void)hipFree(d_beta);
@@ -3049,18 +3076,44 @@ int mcq_run_host(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* 
         HOST_TRY(hipMemcpy(d_beta, p->beta_table, tb, hipMemcpyHostToDevice));
     }
     pd.beta_table = d_beta;
+    mcq_resume fd;
+    if (from) {
+        fd = *from;
+        if (from->state) {
+            HOST_TRY(hipMalloc((void**)&d_state, n * sb));
+            HOST_TRY(hipMemcpy(d_state, from->state, n * sb, hipMemcpyHostToDevice));
+            fd.state = d_state;
+        }
+        if (from->stream) {
+            HOST_TRY(hipMalloc((void**)&d_stream, n * 625 * 4));
+            HOST_TRY(hipMemcpy(d_stream, from->stream, n * 625 * 4, hipMemcpyHostToDevice));
+            fd.stream = d_stream;
+        }
+    }
+    if (stream_out) HOST_TRY(hipMalloc((void**)&d_stream_out, n * 625 * 4));
     float i_ms = 0.f, s_ms = 0.f;
-    rc = mcq_run_device_timed(&pd, d_seeds, &d, d_ws, ws_bytes, nullptr, &i_ms, &s_ms);
+    rc = run_device_timed_impl(&pd, from ? &fd : nullptr, d_seeds, &d, d_ws, ws_bytes, nullptr, &i_ms, &s_ms);
+    if (rc == MCQ_OK && stream_out) rc = mcq_checkpoint_device(&pd, &d, d_ws, ws_bytes, d_stream_out, nullptr);
     if (rc != MCQ_OK) {
         cleanup();
         return rc;
     }
     if (kernel_seconds) *kernel_seconds = (i_ms + s_ms) * 1e-3;
+    if (stream_out) HOST_TRY(hipMemcpy(stream_out, d_stream_out, n * 625 * 4, hipMemcpyDeviceToHost));
     for (auto& b : bufs)
         if (b.host) HOST_TRY(hipMemcpy(b.host, *b.dev, b.bytes, hipMemcpyDeviceToHost));
     cleanup();
     return MCQ_OK;
 #undef HOST_TRY
+}
+
+int mcq_run_host(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, double* kernel_seconds) {
+    return run_host_impl(p, nullptr, seeds, out, nullptr, kernel_seconds);
+}
+
+int mcq_run_host_from(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, uint32_t* stream_out, double* kernel_seconds) {
+    if (!from) return fail(MCQ_EINVAL, "null mcq_resume");
+    return run_host_impl(p, from, seeds, out, stream_out, kernel_seconds);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ import time
 import numpy as np
 
 from . import _lib, abi
+from .checkpoint import Checkpoint
 
 
 # --------------------------------------------------------------------------------------------
@@ -177,6 +178,67 @@ def run_chains(N, n_steps, init_mode, schedule_params, seeds, mcmc_type="full_3d
     return _lib.run_host(params, seeds.astype(np.uint32), trace=trace, states=states)
 
 
+# --------------------------------------------------------------------------------------------
+# chains in segments: the concatenation of the segments IS the unbroken run, bit for bit (include/mcq.h: mcq_resume)
+# --------------------------------------------------------------------------------------------
+def _run_segment(ckpt, n_steps, state, stream_state, trace, states, lanes_per_chain, flags, init_mode="random", init_modes=None,
+                 first_stream_states=None):
+    n_steps = int(n_steps)
+    if n_steps < 0 or ckpt.step + n_steps > ckpt.schedule_steps:
+        raise ValueError(f"a segment of {n_steps} steps from step {ckpt.step} leaves the schedule of {ckpt.schedule_steps} steps")
+    p = ckpt.params(n_steps, trace=trace, lanes_per_chain=lanes_per_chain, flags=flags, init_mode=init_mode, init_modes=init_modes)
+    if first_stream_states is not None:
+        abi.set_stream_states(p, first_stream_states)
+    r = abi.make_resume(p, ckpt.step, ckpt.schedule_steps, state=state, stream_state=stream_state)
+    res, secs = _lib.run_host_from(p, ckpt.seeds, r, checkpoint=True, trace=trace, states=True)
+    ckpt.merge(res, n_steps)
+    if not states:
+        res.pop("best_state"), res.pop("final_state")
+    res["kernel_seconds"] = secs
+    return res, ckpt
+
+
+def start_chains(N, n_steps, init_mode, schedule_params, seeds, schedule_steps=None, mcmc_type="full_3d", trace=True, states=True,
+                 flags=0, lanes_per_chain=0, Q=None, stream_states=None, schedule_sets=None, chains_per_set=None, init_modes=None):
+    """The first `n_steps` steps of chains whose schedule is `schedule_steps` long (default: n_steps): like run_chains, but beta follows the
+    WHOLE schedule and the chains can go on (continue_chains).  Early stopping is off.  `schedule_sets` / `chains_per_set` / `init_modes`
+    run several schedules side by side (abi.make_params_sets; `schedule_params` is then unused).
+
+    Returns (result dict of the segment -- every field relative to the segment, plus `stream_state` and `kernel_seconds` --, Checkpoint)."""
+    seeds = np.asarray(seeds)
+    if seeds.size and (seeds.min() < 0 or seeds.max() > 2**32 - 1):
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    total = int(n_steps) if schedule_steps is None else int(schedule_steps)
+    ckpt = Checkpoint(N, mcmc_type, total, seeds.astype(np.uint32), schedule_params=None if schedule_sets is not None else schedule_params,
+                      schedule_sets=schedule_sets, chains_per_set=chains_per_set, Q=Q, trace=trace)
+    return _run_segment(ckpt, n_steps, None, None, trace, states, lanes_per_chain, flags, init_mode=init_mode, init_modes=init_modes,
+                        first_stream_states=stream_states)
+
+
+def continue_chains(ckpt, n_steps, trace=None, states=True, lanes_per_chain=0, flags=0, N=None, mcmc_type=None, Q=None):
+    """The next `n_steps` steps of the chains of `ckpt` (which is updated and returned): steps [ckpt.step, ckpt.step + n_steps) of the
+    schedule, from the checkpoint's placements and streams.  `trace` defaults to the checkpoint's.  N / mcmc_type / Q, when given, must
+    be the checkpoint's (ValueError otherwise).  Returns (result dict of the segment, ckpt)."""
+    ckpt.require(N=N, mcmc_type=mcmc_type, Q=Q)
+    if ckpt.state is None or ckpt.stream_state is None:
+        raise ValueError("the checkpoint holds no placements / streams to continue from")
+    return _run_segment(ckpt, n_steps, ckpt.state, ckpt.stream_state, ckpt.trace if trace is None else trace, states, lanes_per_chain, flags)
+
+
+def warm_start_chains(N, states_in, seeds, n_steps, schedule_params, schedule_steps=None, mcmc_type="full_3d", trace=True, states=True,
+                      flags=0, lanes_per_chain=0, Q=None, schedule_sets=None, chains_per_set=None):
+    """Chains that start from GIVEN placements (`states_in`: uint8[n_chains][state_bytes] in the final_state layout -- N*N heights, or
+    (i, j, k) per queen), e.g. a known good board to be polished: seeded with `seeds` like any chain, no initialisation draw taken --
+    which is what the reference's latin and exact-Klarner inits do.  Returns (result dict, Checkpoint) like start_chains."""
+    seeds = np.asarray(seeds)
+    if seeds.size and (seeds.min() < 0 or seeds.max() > 2**32 - 1):
+        raise ValueError("Seed must be between 0 and 2**32 - 1")
+    total = int(n_steps) if schedule_steps is None else int(schedule_steps)
+    ckpt = Checkpoint(N, mcmc_type, total, seeds.astype(np.uint32), schedule_params=None if schedule_sets is not None else schedule_params,
+                      schedule_sets=schedule_sets, chains_per_set=chains_per_set, Q=Q, trace=trace)
+    return _run_segment(ckpt, n_steps, np.asarray(states_in, dtype=np.uint8), None, trace, states, lanes_per_chain, flags)
+
+
 def accepted_rejected_steps(res, r):
     """Step indices of accepted / rejected proposals of chain r (experiments.py:329-332)."""
     n = int(res["steps_executed"][r])
@@ -286,7 +348,7 @@ def run_single_chain_board_multithread(args):
 
 def run_experiment(N, n_steps, init_mode, beta_schedule, n_runs, base_seed=0, verbose=False, n_workers=None,
                    schedule_params=None, mcmc_type="full_3d", early_stop_patience=100000, return_steps=True,
-                   lanes_per_chain=0):
+                   lanes_per_chain=0, segment_steps=None):
     """experiments.py:475-573.  Chain r is seeded with base_seed + r and results come back ordered by r.
 
     Returns the reference's 6-tuple (all_histories, best_energies, run_times, all_accepted_steps,
@@ -297,7 +359,12 @@ def run_experiment(N, n_steps, init_mode, beta_schedule, n_runs, base_seed=0, ve
     (they are O(n_runs * n_steps) on the host).
 
     Reference behaviours kept: n_runs > 1 requires schedule_params (experiments.py:505-506);
-    n_runs == 1 drops early_stop_patience (experiments.py:550-558); full_3d ignores it."""
+    n_runs == 1 drops early_stop_patience (experiments.py:550-558); full_3d ignores it.
+
+    segment_steps (not in the reference; default None = one launch): the chains run in segments of at most that many steps
+    (start_chains / continue_chains), the traces are stitched on the host and the same 6-tuple comes back, bit for bit what one
+    launch gives -- and a full trace of 2^24 steps and more, which one launch refuses, becomes possible for callers with the host
+    memory for it.  A board patience that could trigger cannot be carried across segments: pass early_stop_patience=None."""
     if n_runs > 1:
         if schedule_params is None:
             raise ValueError("schedule_params is required for parallel execution when n_runs > 1")
@@ -308,6 +375,9 @@ def run_experiment(N, n_steps, init_mode, beta_schedule, n_runs, base_seed=0, ve
     if n_runs <= 0:
         return [], [], [], [], [], []
     seeds = abi.seeds_for(base_seed, n_runs)
+    if segment_steps is not None:
+        return _run_experiment_segments(N, int(n_steps), init_mode, schedule_params, seeds, mcmc_type, patience, return_steps, lanes_per_chain,
+                                        int(segment_steps), verbose)
     res, secs = run_chains(N, n_steps, init_mode, schedule_params, seeds, mcmc_type=mcmc_type, early_stop_patience=patience,
                            states=False, lanes_per_chain=lanes_per_chain)
     all_histories = [res["energy_hist"][r, : int(res["hist_len"][r])] for r in range(n_runs)]
@@ -326,3 +396,44 @@ def run_experiment(N, n_steps, init_mode, beta_schedule, n_runs, base_seed=0, ve
         for b in best_energies:
             print(b)
     return all_histories, best_energies, run_times, all_acc, all_rej, all_steps_to_best
+
+
+def _run_experiment_segments(N, n_steps, init_mode, schedule_params, seeds, mcmc_type, patience, return_steps, lanes_per_chain, segment_steps, verbose):
+    """run_experiment(..., segment_steps=...): the same chains in segments, stitched."""
+    if segment_steps <= 0 or abi.hist_stride_for(segment_steps) >= abi.MAX_HIST_STRIDE:
+        raise ValueError(f"segment_steps must be positive and leave a trace row below 2^24 entries, got {segment_steps}")
+    if abi.mode_of(mcmc_type) == abi.MODE_BOARD and abi.normalise_patience(patience) >= 0 and abi.normalise_patience(patience) <= n_steps:
+        raise ValueError("early stopping that could trigger cannot be carried across segments: pass early_stop_patience=None")
+    n_runs = len(seeds)
+    hist = [np.empty(n_steps + 1, dtype=np.int32) for _ in range(n_runs)]
+    acc = [[] for _ in range(n_runs)]
+    rej = [[] for _ in range(n_runs)]
+    secs, done, ckpt = 0.0, 0, None
+    while True:
+        n = min(segment_steps, n_steps - done)
+        if ckpt is None:
+            res, ckpt = start_chains(N, n, init_mode, schedule_params, seeds, schedule_steps=n_steps, mcmc_type=mcmc_type, states=False,
+                                     lanes_per_chain=lanes_per_chain)
+        else:
+            res, ckpt = continue_chains(ckpt, n, states=False, lanes_per_chain=lanes_per_chain)
+        secs += res["kernel_seconds"]
+        for r in range(n_runs):
+            if done == 0:
+                hist[r][: n + 1] = res["energy_hist"][r, : n + 1]
+            else:  # entry 0 of a later segment repeats the last entry of the one before
+                hist[r][done + 1: done + n + 1] = res["energy_hist"][r, 1: n + 1]
+            if return_steps:
+                a, j = accepted_rejected_steps(res, r)
+                acc[r].append(a + done), rej[r].append(j + done)
+        done += n
+        if done >= n_steps:
+            break
+    best_energies = [int(b) for b in ckpt.best_energy]
+    if return_steps:
+        all_acc, all_rej = [np.concatenate(a) for a in acc], [np.concatenate(j) for j in rej]
+    else:
+        all_acc, all_rej = [[] for _ in range(n_runs)], [[] for _ in range(n_runs)]
+    if verbose:
+        for b in best_energies:
+            print(b)
+    return hist, best_energies, [secs / n_runs] * n_runs, all_acc, all_rej, [int(s) for s in ckpt.steps_to_best]

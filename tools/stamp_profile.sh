@@ -5,10 +5,11 @@
 # usage: tools/stamp_profile.sh [bench.py args...]
 set -e
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-SRC=$ROOT/monte-carlo-collective_amd/csrc/mcq_hip.hip
+CSRC=$ROOT/monte-carlo-collective_amd/csrc
+SRC="$CSRC/mcq_hip.hip $CSRC/mcq_resume.hip"   # build.SOURCES (the sweep and its C-ABI; the restore / checkpoint kernels it launches)
 LIB=$ROOT/build/libmcq_hip_stamps.so
 mkdir -p $ROOT/build
-if [ ! -f $LIB ] || [ $SRC -nt $LIB ]; then
+if [ ! -f $LIB ] || [ $CSRC/mcq_hip.hip -nt $LIB ] || [ $CSRC/mcq_resume.hip -nt $LIB ] || [ $CSRC/mcq_record.h -nt $LIB ]; then
   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared -DMCQ_STAMPS -o $LIB $SRC
 fi
 [ "$1" = "--build-only" ] && exit 0
