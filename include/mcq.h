@@ -361,6 +361,76 @@ int mcq_checkpoint_device(const mcq_params* p, const mcq_outputs* out, void* wor
 int mcq_run_host_from(const mcq_params* p, const mcq_resume* from, const uint32_t* seeds, const mcq_outputs* out, uint32_t* stream_out,
                       double* kernel_seconds);
 
+/*
+ * Population annealing: the chains of a population are RESAMPLED between two segments (csrc/mcq_population.hip) -- NOT a mode of the
+ * reference, never a default, like Philox and replica exchange.  A run of n_steps steps is cut into segments of S steps
+ * (mcq_run_device_from); at boundary k = 1 .. K - 1 (K = ceil(n_steps / S)), before the segment that starts at step k S, slot m of a
+ * population of R chains [g R, (g + 1) R) takes the PLACEMENT (and with it the energy) of a parent p(m) of the same population.  The
+ * slot keeps its own random stream, its own history and its own running best.  The rule is integer-exact:
+ *   1. dbeta_k = beta(k S) - beta((k - 1) S) >= 0, beta as the sweep reads it (float64, the reference's arithmetic).
+ *   2. the caller's weight table T_k[d] = floor(2^24 exp(-dbeta_k d)) as uint32, d = 0 .. D - 1; D = 1 + the first d with T = 0, at most
+ *      2^16.  T_k[0] = 2^24.
+ *   3. E_r = the segment's final_energy, E_min = the population's minimum, d_r = min(E_r - E_min, D - 1), w_r = T_k[d_r];
+ *      C_r = w_0 + .. + w_r (uint64, slot order), W = C_{R-1}.  R <= 2^19, so that R W < 2^64.
+ *   4. one 32-bit offset word x per (boundary, population): U = floor(x W / 2^32) < W, from the full product.
+ *   5. systematic resampling: p(m) = the smallest r with C_r R > m W + U.
+ *   6. so chain r gets floor(R w_r / W) or ceil(R w_r / W) children, the map m -> p(m) is monotone, and equal weights (dbeta = 0) give
+ *      the identity.
+ * mcq_resample describes ONE boundary.  mcq_resample_device enqueues a few small kernels on the stream: the plan (per population:
+ * min-reduce, table lookup and 64-bit prefix sum in one workgroup, then the search for p(m) with one lane per slot), the row gather
+ * state_out[m] = state_in[parent[m]] -- which cannot run in place: two buffers --, and the per-slot fold of the finished segment's
+ * summary into the run's.  The fold follows the merge rule of
+ * chains in segments: a segment moves best_energy / best_state / steps_to_best (in whole-run steps: first_step + the segment's) only by
+ * a STRICTLY lower energy; n_accepted, near_ties and stream_words (modulo 2^32) add up; first_step == 0 (the first segment) copies.
+ * With state_in == NULL nothing is resampled and only the fold runs (the last segment of a run).
+ */
+#define MCQ_MAX_POPULATION (1 << 19)
+#define MCQ_MAX_RESAMPLE_TABLE (1 << 16)
+#define MCQ_RESAMPLE_WEIGHT_BITS 24
+
+typedef struct mcq_resample {
+    int64_t n_chains;          /* a multiple of population */
+    int64_t population;        /* R: a multiple of 16, <= MCQ_MAX_POPULATION */
+    int64_t state_bytes;       /* bytes of one placement row (mcq_state_bytes_for) */
+    const uint32_t* table;     /* T_k, table_len entries */
+    int64_t table_len;         /* D, 1 .. MCQ_MAX_RESAMPLE_TABLE */
+    const uint32_t* offsets;   /* x, one word per population */
+    const int32_t* energies;   /* [n_chains] final_energy of the finished segment */
+    const uint8_t* state_in;   /* [n_chains][state_bytes] its final_state; NULL = fold only.  16-byte aligned when state_bytes % 16 == 0 */
+    uint8_t* state_out;        /* [n_chains][state_bytes], not state_in; aligned like state_in */
+    int32_t* parent;           /* [n_chains] p(m) as a chain index of the launch (g R + r) */
+    int64_t* stats;            /* [n_chains / population][3]: distinct parents, W, E_min */
+    int32_t* energy_out;       /* optional [n_chains]: energies[parent[m]] (not `energies`) */
+    /* optional fold of the segment's per-slot summary (seg_*, what the segment's mcq_outputs hold) into the run's (run_*);
+     * on when run_best_energy is given, then seg_best_energy, seg_steps_to_best, seg_n_accepted and the matching run_* are required */
+    int64_t first_step;        /* index, in the whole schedule, of the finished segment's step 0 */
+    const int32_t* seg_best_energy;
+    const int64_t* seg_steps_to_best;
+    const int64_t* seg_n_accepted;
+    const int64_t* seg_near_ties;     /* optional, with run_near_ties */
+    const uint32_t* seg_stream_words; /* optional, with run_stream_words */
+    const uint8_t* seg_best_state;    /* optional, with run_best_state; rows of state_bytes, aligned like state_in */
+    int32_t* run_best_energy;
+    int64_t* run_steps_to_best;
+    int64_t* run_n_accepted;
+    int64_t* run_near_ties;
+    uint32_t* run_stream_words;
+    uint8_t* run_best_state;
+} mcq_resample;
+
+/* the message of the last error of the calling thread from the three mcq_resample_* calls below (they do not set mcq_last_error()) */
+const char* mcq_population_last_error(void);
+/* bytes of device scratch mcq_resample_device needs (the prefix sums C_r); 0 on bad arguments */
+size_t mcq_resample_scratch_bytes(const mcq_resample* r);
+/* One boundary on the device: every pointer of `r` and `scratch` (8-byte aligned) are DEVICE pointers.  Enqueued on `hip_stream`;
+ * asynchronous, nothing is copied to the host.  MCQ_EINVAL: a population that is no multiple of 16, exceeds MCQ_MAX_POPULATION or does
+ * not divide n_chains; table_len out of range; a missing pointer; misaligned rows; state_out == state_in.  NOT checked, being on the
+ * device: a table with T[0] = 0 gives W = 0 and every slot of the population the parent g R + R - 1; nothing leaves the arrays. */
+int mcq_resample_device(const mcq_resample* r, void* scratch, size_t scratch_bytes, void* hip_stream);
+/* The plan alone -- steps 3 to 5 -- in pure host code: table, offsets, energies, parent and stats are HOST pointers, the rest of `r`
+ * is ignored.  Equal to the plan kernel bit for bit; exported for the tests the way mcq_stream_layout is. */
+int mcq_resample_plan_host(const mcq_resample* r);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -171,6 +171,13 @@ def lib():
         L.mcq_checkpoint_device.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Outputs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.mcq_run_host_from.restype = C.c_int
         L.mcq_run_host_from.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Resume), C.c_void_p, C.POINTER(abi.Outputs), C.c_void_p, C.POINTER(C.c_double)]
+        L.mcq_population_last_error.restype = C.c_char_p
+        L.mcq_resample_scratch_bytes.restype = C.c_size_t
+        L.mcq_resample_scratch_bytes.argtypes = [C.POINTER(abi.Resample)]
+        L.mcq_resample_device.restype = C.c_int
+        L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.mcq_resample_plan_host.restype = C.c_int
+        L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -186,6 +193,44 @@ def _check(rc):
     if rc == abi.ENOMEM:
         raise MemoryError(msg)
     raise McqError(msg)
+
+
+def _check_population(rc):
+    """_check for the mcq_resample_* calls, which keep their own message (mcq_population_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_population_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def resample_plan_host(energies, population, table, offsets):
+    """mcq_resample_plan_host: the parents population annealing's rule gives the chains of `energies` (int32[n_chains]) in populations of
+    `population`, with the weight table `table` (abi.resample_table) and one offset word per population.  Pure host code, no GPU.
+    Returns (parent int32[n_chains], stats int64[n_populations][3]: distinct parents, W, E_min)."""
+    e = np.ascontiguousarray(energies, dtype=np.int32)
+    t = np.ascontiguousarray(table, dtype=np.uint32)
+    x = np.ascontiguousarray(offsets, dtype=np.uint32)
+    n, R = len(e), int(population)
+    if e.ndim != 1 or t.ndim != 1 or x.ndim != 1:
+        raise ValueError("energies, table and offsets are one-dimensional")
+    if R > 0 and n % R == 0 and len(x) != n // R:
+        raise ValueError("one offset word per population")
+    r = abi.Resample()
+    r.n_chains, r.population, r.table_len = n, R, len(t)
+    parent = np.zeros(n, dtype=np.int32)
+    stats = np.zeros((max(1, n // R) if R > 0 else 1, 3), dtype=np.int64)
+    r.table, r.offsets, r.energies, r.parent, r.stats = t.ctypes.data, x.ctypes.data, e.ctypes.data, parent.ctypes.data, stats.ctypes.data
+    _check_population(lib().mcq_resample_plan_host(C.byref(r)))
+    return parent, stats
+
+
+def resample_device(r, scratch, stream):
+    """mcq_resample_device with a torch uint8 tensor as scratch, enqueued on the torch stream `stream`; asynchronous."""
+    _check_population(lib().mcq_resample_device(C.byref(r), scratch.data_ptr(), scratch.numel(), C.c_void_p(stream.cuda_stream)))
 
 
 def device_count():

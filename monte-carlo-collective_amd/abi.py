@@ -93,6 +93,54 @@ class Resume(C.Structure):
     ]
 
 
+MAX_POPULATION = 1 << 19       # include/mcq.h: MCQ_MAX_POPULATION
+MAX_RESAMPLE_TABLE = 1 << 16   # MCQ_MAX_RESAMPLE_TABLE
+RESAMPLE_WEIGHT_BITS = 24      # MCQ_RESAMPLE_WEIGHT_BITS
+
+
+class Resample(C.Structure):
+    """include/mcq.h: mcq_resample -- one resampling boundary of population annealing"""
+    _fields_ = [
+        ("n_chains", C.c_int64),
+        ("population", C.c_int64),
+        ("state_bytes", C.c_int64),
+        ("table", C.c_void_p),
+        ("table_len", C.c_int64),
+        ("offsets", C.c_void_p),
+        ("energies", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("parent", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("first_step", C.c_int64),
+        ("seg_best_energy", C.c_void_p),
+        ("seg_steps_to_best", C.c_void_p),
+        ("seg_n_accepted", C.c_void_p),
+        ("seg_near_ties", C.c_void_p),
+        ("seg_stream_words", C.c_void_p),
+        ("seg_best_state", C.c_void_p),
+        ("run_best_energy", C.c_void_p),
+        ("run_steps_to_best", C.c_void_p),
+        ("run_n_accepted", C.c_void_p),
+        ("run_near_ties", C.c_void_p),
+        ("run_stream_words", C.c_void_p),
+        ("run_best_state", C.c_void_p),
+    ]
+
+
+def resample_table(dbeta):
+    """The weight table of one boundary (include/mcq.h, population annealing, step 2): T[d] = floor(2^24 exp(-dbeta d)) as uint32 for
+    d = 0 .. D - 1, D = 1 + the first d with T = 0, at most 2^16.  NumPy's exp / floor on float64."""
+    dbeta = float(dbeta)
+    if not dbeta >= 0.0:
+        raise ValueError(f"population annealing needs a schedule that does not decrease: a boundary has dbeta = {dbeta}")
+    d = np.arange(MAX_RESAMPLE_TABLE, dtype=np.float64)
+    t = np.floor(float(1 << RESAMPLE_WEIGHT_BITS) * np.exp(-dbeta * d)).astype(np.uint32)
+    zero = np.flatnonzero(t == 0)
+    return np.ascontiguousarray(t[: int(zero[0]) + 1] if len(zero) else t)
+
+
 class PackSlot(C.Structure):
     """include/mcq.h: mcq_pack_slot -- where one job's fields sit in the packed summary tensor (word offsets, -1 = absent)"""
     _fields_ = [("counters", C.c_int64), ("min_slot", C.c_int64), ("best", C.c_int64), ("stb", C.c_int64), ("stats", C.c_int64)]

@@ -244,19 +244,33 @@ def write_best_heights(heights, N, path):
 
 
 def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.0, base_seed=42, init_mode="random",
-                    out_dir="competition_results", runner=None, timestamp=None):
+                    out_dir="competition_results", runner=None, timestamp=None, resample_every=None, population=None, resample_seed=0):
     """competition.py:143-187: board chains with linear annealing beta_start -> beta_end, seeds base_seed + r; the board
     of the run with the lowest best energy is written to {out_dir}/best_heights_{N}_{timestamp}.txt.
-    Returns (best energy, heights, path)."""
-    import time
+    Returns (best energy, heights, path).
 
-    runner = _runner_or_default(runner)
+    resample_every (not in the reference; None = the reference's independent chains, exactly as without the argument): the runs are
+    the slots of a population annealing (population.anneal_population) resampled every that many steps inside populations of
+    `population` chains (None: all runs) with the offset words of `resample_seed`; `runner` is then unused."""
     sp = {"type": "linear_annealing", "beta_start": beta_start, "beta_end": beta_end}
+    if resample_every is not None:
+        from . import population as _pop
+
+        res, _ = _pop.anneal_population(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), resample_every, population=population,
+                                        resample_seed=resample_seed, mcmc_type="board", trace=False, states=True)
+        return _write_competition(res, N, out_dir, timestamp)
+    runner = _runner_or_default(runner)
     try:
         res, _ = runner(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), mcmc_type="board", early_stop_patience=None,
                         trace=False, states=True)
     except TypeError:  # injected runners without a `states` argument return the states anyway
         res, _ = runner(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), mcmc_type="board", early_stop_patience=None, trace=False)
+    return _write_competition(res, N, out_dir, timestamp)
+
+
+def _write_competition(res, N, out_dir, timestamp):
+    import time
+
     r = int(np.argmin(res["best_energy"]))  # first run with the minimum, like min() over the runs in order
     heights = np.asarray(res["best_state"][r]).reshape(N, N)
     stamp = timestamp if timestamp is not None else time.strftime("%Y%m%d_%H%M%S")
