@@ -223,6 +223,13 @@ int32_t mcq_default_lanes_n(int32_t mode, int32_t N);
 int32_t mcq_effective_lanes(const mcq_params* p);
 /* SIMDs of the current device (4 per compute unit; 1024 when no device answers): what the small-launch rule compares with */
 int32_t mcq_device_simds(void);
+/* Inspection: the instantiation of the sweep kernel a launch with these parameters takes on the current device.  variant[13]: the
+ * kernel's template arguments in their order -- MODE, G (= mcq_effective_lanes), PATIENCE, NT, REDUCED, PHILOX, NC, EXCH, CAND5,
+ * EARLYU, SLIM, CNT, WIDE (bools as 0 / 1) --, *lds_bytes: the dynamic LDS of a workgroup (one wavefront).  Pure host code: it looks
+ * at the device's SIMD count only (1024 when no device answers).  Every variant gives the same results; this exists so that the
+ * choice, which only speed depends on, can be tested.  Returns what mcq_run_device would refuse these parameters with before it
+ * enqueues anything (bad arguments, a lane count the mode does not run, a chain state beyond the LDS), the text in mcq_last_error. */
+int mcq_sweep_variant(const mcq_params* p, int32_t variant[13], int64_t* lds_bytes);
 
 /* bytes of one chain's state record in best_state / final_state; 0 on bad arguments.  mcq_state_bytes: Q = N*N queens;
  * mcq_state_bytes_for: the parameter block's own count (n_queens). */

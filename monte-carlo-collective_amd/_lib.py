@@ -140,6 +140,8 @@ def lib():
         L.mcq_effective_lanes.restype = C.c_int32
         L.mcq_effective_lanes.argtypes = [C.POINTER(abi.Params)]
         L.mcq_device_simds.restype = C.c_int32
+        L.mcq_sweep_variant.restype = C.c_int
+        L.mcq_sweep_variant.argtypes = [C.POINTER(abi.Params), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         L.mcq_state_bytes.restype = C.c_size_t
         L.mcq_state_bytes.argtypes = [C.c_int32, C.c_int32]
         L.mcq_state_bytes_for.restype = C.c_size_t
@@ -240,6 +242,14 @@ def device_count():
 def effective_lanes(params):
     """Lanes of a wavefront per chain a launch with these parameters runs with on the current device."""
     return int(lib().mcq_effective_lanes(C.byref(params)))
+
+
+def sweep_variant(params):
+    """mcq_sweep_variant: the instantiation of the sweep kernel a launch with these parameters takes on the current device, as a dict of
+    its template arguments (abi.SWEEP_VARIANT_FIELDS, in the kernel's order) and "lds_bytes", the dynamic LDS of a workgroup.  No GPU needed."""
+    v, lds = (C.c_int32 * len(abi.SWEEP_VARIANT_FIELDS))(), C.c_int64()
+    _check(lib().mcq_sweep_variant(C.byref(params), v, C.byref(lds)))
+    return dict(zip(abi.SWEEP_VARIANT_FIELDS, v), lds_bytes=int(lds.value))
 
 
 def beta_table_device(params):

@@ -36,6 +36,8 @@ def flag_priority(p):
     return (int(p) & 3) << FLAG_PRIORITY_SHIFT
 
 
+# mcq_sweep_variant: the template arguments of mcq_sweep_kernel, in the kernel's order
+SWEEP_VARIANT_FIELDS = ("MODE", "G", "PATIENCE", "NT", "REDUCED", "PHILOX", "NC", "EXCH", "CAND5", "EARLYU", "SLIM", "CNT", "WIDE")
 MIN_N, MAX_N, MAX_N_BOARD = 2, 64, 128  # include/mcq.h: full_3d up to 64, boards up to 128
 MAX_HIST_STRIDE = 1 << 24  # a full trace row (hist_stride entries) must stay below this: include/mcq.h
 

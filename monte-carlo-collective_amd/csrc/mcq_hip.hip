@@ -146,7 +146,7 @@ struct KArgs {
     int low_water;            // stream upkeep runs when some chain of the wavefront holds fewer ready words than this
     int init_words;           // init kernel: LDS words per chain
     const double* exch_ladder;  // [exch_R] beta multipliers per rung (workspace)
-    int dry;                  // launch_sweep: check that the chosen variant fits the device and return without launching
+    int reserved0;            // unused (was a dry-run switch of the launcher); kept so that the layout of this kernel argument stays what it was
     uint16_t* qtab;           // full_3d: the queens of every chain as i | j << 5 | k << 10, [n_chains][qtab_stride] (workspace; the sweep variants that
     int qtab_stride;          // keep their queen table out of LDS work on it, the init kernel fills it).  Beyond N = 32: uint32 entries i | j << 8 | k << 16
     uint32_t* perm;           // full_3d beyond N = 32, random init: the N^3 cells np.random.choice permutes, one slice per chain of an init launch (workspace)
@@ -2104,6 +2104,15 @@ int gcd_int(int a, int b) {
     return a;
 }
 
+// KArgs::klarner_M for an init mode: 0 unless it is Klarner's and N shares a factor with 210, then the largest core edge below N that
+// shares none (-1: there is none)
+int klarner_core(int init, int N) {
+    if (init != MCQ_INIT_KLARNER || gcd_int(N, 210) == 1) return 0;
+    for (int m = N - 1; m > 0; m--)
+        if (gcd_int(m, 210) == 1) return m;
+    return -1;
+}
+
 unsigned host_mask(unsigned m) {
     unsigned mask = m;
     mask |= mask >> 1, mask |= mask >> 2, mask |= mask >> 4, mask |= mask >> 8, mask |= mask >> 16;
@@ -2244,24 +2253,6 @@ size_t red_bytes(const mcq_params* p) { return n_sets_of(p) * red_set_bytes(p); 
 constexpr size_t PACE_BYTES = 2048 * 16 * 4;  // 8 XCC x 4 SE x 16 CU x 4 SIMD rows of 16 wave slots
 constexpr size_t LADDER_BYTES = 16 * 8;       // replica exchange: the beta multipliers of a ladder
 
-// LDS words per chain.  board: the diagonal probes read up to N-1 bytes before / after the heights, (N+2)/4 spare words on each
-// side keep those (discarded) reads inside the chain's own slice; full_3d: pad | column words | pad | queens (uint16).
-int chain_lds_words_for(int N, int mode, bool narrow, int Q = 0, bool slim = false, bool counters = false, bool wide = false) {
-    const int NN = N * N, pad = (N + 3) & ~3;
-    if (Q <= 0) Q = NN;  // full_3d: the queens (mcq_params.n_queens); N * N by default
-    int w = LDS_STATE;
-    if (mode == MCQ_MODE_BOARD) w += (NN + 3) / 4 + (N + 2) / 4 + (counters ? (2 * NN + 6 * N * (2 * N - 1) + 4 * (2 * N - 1) * (2 * N - 1) + 3) / 4 : 0);
-    else if (wide) w += 2 * (2 * pad + NN);  // WIDE: pad | 64-bit column words | pad; the queens are in global memory
-    else if (slim) w = 16 + 4 + RING + (NN + 1) / 2;  // SLIM: stage[16] | cold[4] | ring[64] | 16-bit column words, no pads; the queens are in global memory
-    else w += (narrow ? (2 * pad + NN + 1) / 2 : 2 * pad + NN) + (Q + 1) / 2;
-    w = (w + 3) & ~3;  // 16-byte multiple: the staging block and the ring are accessed with 128-bit LDS operations
-    // The chains of a wavefront make many accesses at the SAME offset of their slices (history staging, cold scalars, ring appends):
-    // a stride of 4 mod 8 words puts the 8 chains of a 32-lane access group on 8 different banks; 0 mod 8 would serialise them
-    // (A/B on the headline problem, same box: profiles/r02_lds_stride_ab.txt, r02_lds_stride_pmc.txt).
-    if (w % 8 == 0) w += 4;
-    return w;
-}
-
 // mcq_resume (include/mcq.h): what a call that runs a segment of a longer schedule, or starts from given placements, can take
 int validate_resume(const mcq_params* p, const mcq_resume* from) {
     int rc = validate(p);
@@ -2285,21 +2276,13 @@ int build_args(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* ou
     memset(a, 0, sizeof *a);
     a->N = p->N, a->Q = queens_of(p), a->NN = p->N * p->N, a->mode = p->mode, a->init = p->init, a->sched = p->sched, a->flags = p->flags, a->rng = p->rng;
     a->maskN = host_mask((unsigned)(p->N - 1)), a->maskQ = host_mask((unsigned)(a->Q - 1));
-    a->klarner_M = 0;
-    if (p->init == MCQ_INIT_KLARNER && gcd_int(p->N, 210) != 1) {
-        for (int m = p->N - 1; m > 0; m--)
-            if (gcd_int(m, 210) == 1) {
-                a->klarner_M = m;
-                break;
-            }
-        if (a->klarner_M == 0) return fail(MCQ_EINVAL, "no Klarner core below N");
-    }
+    a->klarner_M = klarner_core(p->init, p->N);
+    if (a->klarner_M < 0) return fail(MCQ_EINVAL, "no Klarner core below N");
     a->state_bytes = (int)state_bytes_of(p);
     a->rec_words = rec_words_for(p);
     // board: the diagonal probes read up to N-1 bytes before / after the heights; (N+2)/4 spare words on each
     // side keep those (discarded) reads inside the chain's own LDS slice.
     a->full_pad = (p->N + 3) & ~3;
-    a->chain_lds_words = chain_lds_words_for(p->N, p->mode, false, a->Q);  // full_3d: the launcher picks the 16-bit layout where it applies
     a->beta_const = p->beta_const, a->beta_start = p->beta_start, a->beta_end = p->beta_end;
     a->n_steps = p->n_steps, a->n_chains = p->n_chains;
     a->step0 = 0, a->sched_steps = p->n_steps;
@@ -2360,224 +2343,364 @@ int effective_lanes(const mcq_params* p) {
     return G;
 }
 
-template <int MODE, int G, bool PATIENCE, int NT, bool REDUCED, bool PHILOX = false, int NC = 0, bool EXCH = false, bool CAND5 = false, bool EARLYU = false, bool SLIM = false, bool CNT = false,
-          bool WIDE = false>
-int launch_sweep(const KArgs& a0, hipStream_t s) {
-    constexpr int CPB = 64 / G;  // one wavefront per workgroup: chains never interact, so no barrier exists
+// One instantiation of mcq_sweep_kernel: a field per template parameter, in the kernel's order.
+struct SweepVariant {
+    int mode, g;
+    bool patience;
+    int nt;
+    bool reduced, philox;
+    int nc;
+    bool exch, cand5, earlyu, slim, cnt, wide;
+};
+bool operator==(const SweepVariant& a, const SweepVariant& b) {
+    return a.mode == b.mode && a.g == b.g && a.patience == b.patience && a.nt == b.nt && a.reduced == b.reduced && a.philox == b.philox && a.nc == b.nc && a.exch == b.exch &&
+           a.cand5 == b.cand5 && a.earlyu == b.earlyu && a.slim == b.slim && a.cnt == b.cnt && a.wide == b.wide;
+}
+
+// LDS words per chain.  board: the diagonal probes read up to N-1 bytes before / after the heights, (N+2)/4 spare words on each
+// side keep those (discarded) reads inside the chain's own slice; full_3d: pad | column words | pad | queens (uint16).
+// The layout follows from the variant as the kernel derives it from its template parameters (NARROW, SLIM, CNT, WIDE); Q: the queens of a full_3d chain.
+int chain_lds_words_for(const SweepVariant& v, int N, int Q) {
+    const int NN = N * N, pad = (N + 3) & ~3;
+    const bool narrow = v.mode == MCQ_MODE_FULL3D && v.nt > 0;  // N <= 16: 16-bit column words
+    int w = LDS_STATE;
+    if (v.mode == MCQ_MODE_BOARD) w += (NN + 3) / 4 + (N + 2) / 4 + (v.cnt ? (2 * NN + 6 * N * (2 * N - 1) + 4 * (2 * N - 1) * (2 * N - 1) + 3) / 4 : 0);
+    else if (v.wide) w += 2 * (2 * pad + NN);  // WIDE: pad | 64-bit column words | pad; the queens are in global memory
+    else if (v.slim) w = 16 + 4 + RING + (NN + 1) / 2;  // SLIM: stage[16] | cold[4] | ring[64] | 16-bit column words, no pads; the queens are in global memory
+    else w += (narrow ? (2 * pad + NN + 1) / 2 : 2 * pad + NN) + (Q + 1) / 2;
+    w = (w + 3) & ~3;  // 16-byte multiple: the staging block and the ring are accessed with 128-bit LDS operations
+    // The chains of a wavefront make many accesses at the SAME offset of their slices (history staging, cold scalars, ring appends):
+    // a stride of 4 mod 8 words puts the 8 chains of a 32-lane access group on 8 different banks; 0 mod 8 would serialise them
+    // (A/B on the headline problem, same box: profiles/r02_lds_stride_ab.txt, r02_lds_stride_pmc.txt).
+    if (w % 8 == 0) w += 4;
+    return w;
+}
+
+// What the choice of a variant looks at: the fields of a validated parameter block, as KArgs holds them.
+struct SweepFacts {
+    int mode, N, Q, rng;  // Q: queens_of()
+    unsigned flags;
+    bool red;             // trace == REDUCED
+    long long patience, n_steps, n_chains, exch_every;
+};
+SweepFacts sweep_facts(const mcq_params* p) {
+    SweepFacts f;
+    f.mode = p->mode, f.N = p->N, f.Q = queens_of(p), f.rng = p->rng, f.flags = p->flags, f.red = p->trace == MCQ_TRACE_REDUCED;
+    f.patience = p->mode == MCQ_MODE_BOARD ? p->patience : -1;  // full_3d ignores early_stop_patience (experiments.py:199-279)
+    f.n_steps = p->n_steps, f.n_chains = p->n_chains, f.exch_every = p->exchange_every;
+    return f;
+}
+
+// The variant a launch of G lanes per chain takes on a device of `simds` SIMDs, or a refusal (the code, the text in mcq_last_error).
+// Every variant computes the same results; the choice is about speed alone.  A variant starts as the run-time probe loop with
+// nothing specialised (all fields zero but mode and g) and each rule below names what it sets.  The rows this can return are
+// SWEEP_TABLE's: a combination that is not built is an error (plan_sweep), never another kernel.
+int select_sweep_variant(const SweepFacts& f, int G, int simds, SweepVariant* out) {
+    const int N = f.N;
+    const bool board = f.mode == MCQ_MODE_BOARD, full = !board, red = f.red, philox = f.rng == MCQ_RNG_PHILOX4X32_10;
+    const bool n12 = N == 12 && (board || f.Q == 144);  // N as a compile-time constant: the full_3d kernels take Q = N^2 with it
+    // a patience beyond n_steps can never stop a chain: the plain variants give the same results
+    const bool pat = board && f.patience >= 0 && f.patience <= f.n_steps;
+    if (G == 2 && full) return fail(MCQ_EINVAL, "lanes_per_chain 2 applies to mcmc_type board");
+    SweepVariant v = {};
+    v.mode = f.mode, v.g = G;
+
+    if (f.exch_every > 0) {
+        // Replica exchange (never a default, not a mode of the reference): the run-time probe loop for every size, plus the two
+        // single_N shapes of BASELINE (board N = 12 at 4 lanes, full_3d N = 12 at 8) with their unrolled steps.
+        // (validate(): no early stop, trace none or i32)
+        v.exch = true, v.philox = philox;
+        if (!philox && n12 && ((board && G == 4) || (full && G == 8))) v.nt = 3, v.nc = 12;
+    } else if (philox) {
+        // Philox mode (evidence / fast mode, never the reference's stream): the variants of BASELINE's two single_N shapes are
+        // specialised (board N = 9..12 at 4 lanes, full_3d N = 9..12 at 8 lanes, no early stop, full or no trace); everything else takes
+        // the run-time probe loop.
+        v.philox = true, v.patience = pat, v.reduced = red;
+        if (!pat && !red && (N + 3) / 4 == 3 && ((board && G == 4) || (full && G == 8))) v.nt = 3, v.nc = n12 ? 12 : 0;
+    } else if (full) {  // no early stop (experiments.py:199-279)
+        v.reduced = red;
+        if (N > 32) {  // 64-bit column words (validate(): 16 lanes per chain, NumPy's stream, no exchange)
+            if (G != 16) return fail(MCQ_EINVAL, "full_3d beyond N = 32 runs at 16 lanes per chain");
+            v.wide = true;
+        } else if (G == 8 && (red ? (N + 3) / 4 == 3 : N <= 16)) {
+            // N <= 16: 16-bit column words, four lanes around each of the two cells, ceil(N / 4) unrolled passes.  The reduced trace has
+            // the three-pass kernel only: BASELINE config 3's shape
+            v.nt = (N + 3) / 4, v.nc = n12 ? 12 : 0;
+        } else if (G == 4 && N > 8 && N <= 12) {
+            // the slim layout (N = 9..12): two lanes around each of the two cells, ceil(N / 2) unrolled passes, the queens in global memory.
+            // (65 536 chains x 20 000 steps against 8 lanes: N = 9 53.2 / 65.4 ms, N = 10 49.6 / 62.6, N = 11 60.3 / 62.9, N = 12 52.1 / 59.8;
+            // seven and eight passes spill and lose -- N = 13 129 / 68 ms, N = 16 109 / 91: profiles/r04_full3d_slim.txt)
+            // (every trace mode: the reduced trace is what the drivers' statistics runs take)
+            v.slim = true, v.nt = (N + 1) / 2, v.nc = n12 ? 12 : 0;
+        }
+    } else if (G == 2) {  // 32 chains per wavefront, ceil(N / 2) packed probe passes
+        v.patience = pat, v.reduced = red;
+        if (N == 12 && !(pat && red)) {  // the size of BASELINE config 2
+            v.nt = 6, v.nc = 12;
+        } else if (!pat && !red && N <= 12) {
+            // the other sizes up to N = 12 without early stop and with a full trace or none: what a job list takes for its SHORT launches when it
+            // balances the lanes of launches that run side by side (half the wavefronts of 4 lanes, a longer step: jobs.plan_lanes)
+            v.cand5 = N <= 5;  // (five candidates for new_k, like the 4-lane kernels of N <= 5)
+            v.nt = N <= 4 ? 2 : (N + 1) / 2;
+        }
+    } else if (G == 4) {
+        v.patience = pat, v.reduced = red;
+        const int nt = (N + 3) / 4;  // straight-line probe blocks for the common board sizes: N = 2..4, 5..8, ... 21..24
+        if ((f.flags & MCQ_FLAG_LINE_COUNTERS) && N <= 8 && !red) {
+            // dE from line counters (MCQ_FLAG_LINE_COUNTERS; N <= 8, NumPy's stream, plain or early-stop, full or no trace): see CNT at the kernel
+            v.cnt = true, v.cand5 = N <= 5;
+        } else if (!red && N <= 5) {
+            // five candidates for new_k: the small cells of measure_min_energy_vs_N (BASELINE config 4), with or without early stop
+            v.cand5 = true, v.nt = N <= 4 ? 1 : 2;
+        } else if (pat) {
+            // early stopping -- the reference's default early_stop_patience = 100000 -- has its own unrolled variants for the
+            // sizes that default to 4 lanes (full or no trace)
+            if (!red && nt <= 3) v.nt = nt, v.nc = n12 ? 12 : 0;
+        } else if (n12) {  // the size of BASELINE config 2: N as a compile-time constant
+            v.nt = 3, v.nc = 12;
+        } else if (!red && (N == 17 || N == 18 || N == 20)) {
+            // the long cells of measure_min_energy_vs_N (BASELINE configs[3]): N as a compile-time constant (125 / 119 / 118 VGPRs and 10 / 7 / 4
+            // spilled SGPRs against 128 / 40 of the generic five-pass variant; N = 19 is left out: its instantiation spills 324 VGPRs)
+            v.nt = 5, v.nc = N;
+        } else if (nt <= 6) {
+            // (up to N = 16: packed 16-bit masks); from four passes on the reduced-trace variants would spill and take the loop
+            v.nt = red && nt >= 4 ? 0 : nt;
+        }
+    } else if (G == 8) {  // larger boards run 8 lanes per chain by default: 2, 3 or 4 straight-line probe passes (N = 9..16 packed, 17..24, 25..32)
+        v.patience = pat, v.reduced = red;
+        // (a launch that leaves the device at most half full -- two wavefronts per SIMD -- takes the variants that request the probe
+        // heights early: see EARLY_PROBES in the kernel)
+        const bool roomy = (f.n_chains + 7) / 8 <= 2LL * simds;
+        const int nt = N <= 16 ? 2 : N <= 24 ? 3 : 4;
+        if (N > 8 && N <= 32 && !(pat && red) && !(red && nt == 4)) {  // (the reduced trace: without early stop and up to three passes)
+            v.nt = nt, v.earlyu = nt == 3 && roomy;
+            if (red && N == 24) v.nc = 24;  // BASELINE config 5: the beta-pair driver's shape (N = 24, reduced trace)
+        }
+    } else {  // G == 16: 4 chains per wavefront: one packed probe pass up to N = 16, two unpacked ones up to N = 32
+        v.patience = pat, v.reduced = red;
+        // (what a launch far below the device's capacity takes -- 16 384 chains of N = 24, the per-GPU shape of BASELINE configs[4], are
+        // four wavefronts per SIMD this way; before round 4 these widths ran the run-time probe loop)
+        const bool roomy = (f.n_chains + 3) / 4 <= 2LL * simds;
+        if (!pat && N <= 16) {
+            v.nt = 1;
+        } else if (!pat && N <= 32) {
+            v.nt = 2, v.nc = red && N == 24 ? 24 : 0, v.earlyu = !red && roomy;
+        }
+    }
+    *out = v;
+    return MCQ_OK;
+}
+
+// Every instantiation of mcq_sweep_kernel the library holds: a row names the thirteen template arguments once, as the key
+// select_sweep_variant's answer is looked up by and as the kernel to launch.  133 rows.  (The two rows marked "never selected" are
+// built because the dispatch that preceded this table named them; they stay so that the code object stays what it was.)
+struct SweepRow {
+    SweepVariant v;
+    void (*kernel)(KArgs);
+};
+#define SWEEP_ROW(...) {SweepVariant{__VA_ARGS__}, &mcq_sweep_kernel<__VA_ARGS__>}
+const SweepRow SWEEP_TABLE[] = {
+    // board, 2 lanes per chain
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   2, false,  false, 0,  false, true,  false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   3, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   3, false,  false, 0,  false, true,  false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   4, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   5, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   6, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   6, false,  false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   6, true,   false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  true,    6, false,  false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   0, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  true,    0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  true,    0, true,   false, 0,  false, false, false, false, false, false),
+    // board, 4 lanes per chain
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   1, false,  false, 0,  false, false, false, false, false, false),  // never selected: N <= 4 takes CAND5
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   1, false,  false, 0,  false, true,  false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   1, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    1, false,  false, 0,  false, false, false, false, false, false),  // never selected: N <= 4 takes CAND5
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    1, false,  false, 0,  false, true,  false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   2, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   2, false,  false, 0,  false, true,  false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   2, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    2, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    2, false,  false, 0,  false, true,  false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    3, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, false,  false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, true,   false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    3, false,  false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   4, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   5, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   5, false,  false, 17, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   5, false,  false, 18, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   5, false,  false, 20, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   6, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    0, true,   false, 0,  false, false, false, false, false, false),
+    // board, 8 lanes per chain
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   2, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   2, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    2, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   3, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   3, false,  false, 0,  false, false, true,  false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   3, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   3, true,   false, 0,  false, false, true,  false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    3, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    3, false,  false, 0,  false, false, true,  false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   3, true,   false, 24, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   3, true,   false, 24, false, false, true,  false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   4, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    4, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   0, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    0, true,   false, 0,  false, false, false, false, false, false),
+    // board, 16 lanes per chain
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   1, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   1, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   2, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   2, false,  false, 0,  false, false, true,  false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   2, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   2, true,   false, 24, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   0, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, true,    0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, true,    0, true,   false, 0,  false, false, false, false, false, false),
+    // full_3d narrow layout (N <= 16, 8 lanes, 16-bit column words)
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   1, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   2, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, false,  false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, true,   false, 12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   4, false,  false, 0,  false, false, false, false, false, false),
+    // full_3d run-time probe loop (32-bit column words)
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   0, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   0, true,   false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, false,  false, 0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, true,   false, 0,  false, false, false, false, false, false),
+    // full_3d slim layout (N = 9..12, 4 lanes, the queens in the workspace)
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   5, false,  false, 0,  false, false, false, true,  false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   5, true,   false, 0,  false, false, false, true,  false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   6, false,  false, 0,  false, false, false, true,  false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   6, true,   false, 0,  false, false, false, true,  false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   6, false,  false, 12, false, false, false, true,  false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   6, true,   false, 12, false, false, false, true,  false, false),
+    // full_3d beyond N = 32: 64-bit column words, 16 lanes
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, false,  false, 0,  false, false, false, false, false, true),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, true,   false, 0,  false, false, false, false, false, true),
+    // board, 4 lanes, dE from line counters (MCQ_FLAG_LINE_COUNTERS, N <= 8)
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, false,  false, 0,  false, false, false, false, true,  false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, false,  false, 0,  false, true,  false, false, true,  false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    0, false,  false, 0,  false, false, false, false, true,  false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    0, false,  false, 0,  false, true,  false, false, true,  false),
+    // Philox stream (the two single_N shapes of BASELINE unrolled; the run-time probe loop otherwise)
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  true,    0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  true,    0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, false,  true,  12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  true,    0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  true,    0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, true,    0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, true,    0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, false,  true,  12, false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   0, true,   true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, false,  true,  0,  false, false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, true,   true,  0,  false, false, false, false, false, false),
+    // replica exchange (run-time probe loop for every width; the two single_N shapes of BASELINE unrolled)
+    //        MODE             G   PATIENCE NT REDUCED PHILOX NC  EXCH   CAND5  EARLYU SLIM   CNT    WIDE
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  2,  false,   0, false,  true,  0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   3, false,  false, 12, true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  4,  false,   0, false,  true,  0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  8,  false,   0, false,  true,  0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_BOARD,  16, false,   0, false,  true,  0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 4,  false,   0, false,  true,  0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   3, false,  false, 12, true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 8,  false,   0, false,  true,  0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, false,  false, 0,  true,  false, false, false, false, false),
+    SWEEP_ROW(MCQ_MODE_FULL3D, 16, false,   0, false,  true,  0,  true,  false, false, false, false, false),
+};
+#undef SWEEP_ROW
+static_assert(sizeof SWEEP_TABLE / sizeof SWEEP_TABLE[0] == 133, "a change of what is instantiated changes the code object: DESIGN.md 4.2 and the register table follow");
+
+// What a launch with a validated parameter block runs on the current device: the variant select_sweep_variant names, its kernel from
+// the table, and the LDS it asks for -- or the refusal of a variant that does not fit the 160 KB of a CU.  Nothing is enqueued here.
+struct SweepPlan {
+    SweepVariant v;
+    void (*kernel)(KArgs);
+    int chain_lds_words;  // KArgs::chain_lds_words
+    size_t lds_bytes;     // dynamic LDS of a workgroup
+};
+int plan_sweep(const mcq_params* p, SweepPlan* plan) {
+    const SweepFacts f = sweep_facts(p);
+    const int rc = select_sweep_variant(f, effective_lanes(p), device_simds(), &plan->v);
+    if (rc != MCQ_OK) return rc;
+    const SweepVariant& v = plan->v;
+    plan->kernel = nullptr;
+    for (const SweepRow& r : SWEEP_TABLE)
+        if (r.v == v) plan->kernel = r.kernel;
+    if (!plan->kernel) {  // a hole in the table is an error of this file, never a reason to run another kernel
+        char args[96];
+        snprintf(args, sizeof args, "%d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d, %d", v.mode, v.g, v.patience, v.nt, v.reduced, v.philox, v.nc, v.exch, v.cand5, v.earlyu, v.slim, v.cnt, v.wide);
+        return fail(MCQ_EDEVICE, "internal error: the selected mcq_sweep_kernel<%s> is not in the table of built variants", args);
+    }
+    const int CPB = 64 / v.g;  // one wavefront per workgroup: chains never interact, so no barrier exists
+    plan->chain_lds_words = chain_lds_words_for(v, f.N, f.Q);
+    plan->lds_bytes = (size_t)CPB * plan->chain_lds_words * 4 + (v.slim ? 64 : 0);  // (SLIM: the pad behind the last chain's column table)
+    if (plan->lds_bytes > 160 * 1024)
+        return fail(MCQ_EINVAL, v.mode == MCQ_MODE_FULL3D && f.Q != f.N * f.N ? "chain state does not fit in LDS (n_queens: the queen table of %s chains per wavefront exceeds 160 KB; more lanes_per_chain halve it)"
+                                                                                : "chain state does not fit in LDS (%s chains per wavefront)", v.g == 2 ? "32" : v.g == 4 ? "16" : v.g == 8 ? "8" : "4");
+    return MCQ_OK;
+}
+
+int launch_sweep(const SweepPlan& plan, const KArgs& a0, hipStream_t s) {
+    const int CPB = 64 / plan.v.g;
     KArgs a = a0;
+    a.chain_lds_words = plan.chain_lds_words;
     // Pacing pays when a SIMD holds several wavefronts of this launch (they can only see each other); a launch that puts less
     // than two wavefronts on a SIMD would pay for the checkpoints and gain nothing.
     const long long waves = (a.n_chains + CPB - 1) / CPB;
     if (waves < 2LL * device_simds() && !(a.flags & MCQ_FLAG_SHARED_PACING)) a.pace = nullptr;
-    const size_t lds = (size_t)CPB * a.chain_lds_words * 4 + (SLIM ? 64 : 0);  // (SLIM: the pad behind the last chain's column table)
-    if (lds > 160 * 1024)
-        return fail(MCQ_EINVAL, MODE == MCQ_MODE_FULL3D && a.Q != a.NN ? "chain state does not fit in LDS (n_queens: the queen table of %s chains per wavefront exceeds 160 KB; more lanes_per_chain halve it)"
-                                                                        : "chain state does not fit in LDS (%s chains per wavefront)", G == 2 ? "32" : G == 4 ? "16" : G == 8 ? "8" : "4");
-    if (a.dry) return MCQ_OK;
-    HIP_TRY(hipFuncSetAttribute((const void*)mcq_sweep_kernel<MODE, G, PATIENCE, NT, REDUCED, PHILOX, NC, EXCH, CAND5, EARLYU, SLIM, CNT, WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned grid = (unsigned)((a.n_chains + CPB - 1) / CPB);
-    hipLaunchKernelGGL((mcq_sweep_kernel<MODE, G, PATIENCE, NT, REDUCED, PHILOX, NC, EXCH, CAND5, EARLYU, SLIM, CNT, WIDE>), dim3(grid), dim3(64), lds, s, a);
+    HIP_TRY(hipFuncSetAttribute((const void*)plan.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes));
+    hipLaunchKernelGGL(plan.kernel, dim3((unsigned)waves), dim3(64), plan.lds_bytes, s, a);
     HIP_TRY(hipGetLastError());
     return MCQ_OK;
-}
-
-// Philox mode (evidence / fast mode, never the reference's stream): the variants of BASELINE's two single_N shapes are
-// specialised (board N = 9..12 at 4 lanes, full_3d N = 9..12 at 8 lanes, no early stop, full or no trace); everything else takes
-// the run-time probe loop.
-template <int MODE, int G>
-int launch_sweep_philox(const KArgs& a, hipStream_t s) {
-    if constexpr (MODE == MCQ_MODE_FULL3D) {
-        if constexpr (G == 8) {
-            if (!a.red && (a.N + 3) / 4 == 3) {
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q);
-                return a.N == 12 && a.Q == 144 ? launch_sweep<MODE, G, false, 3, false, true, 12>(b, s) : launch_sweep<MODE, G, false, 3, false, true>(b, s);
-            }
-        }
-        return a.red ? launch_sweep<MODE, G, false, 0, true, true>(a, s) : launch_sweep<MODE, G, false, 0, false, true>(a, s);
-    } else {
-        const bool pat = a.patience >= 0 && a.patience <= a.n_steps;  // a patience beyond n_steps can never stop a chain: the plain variants give the same results
-        if constexpr (G == 4) {
-            if (!pat && !a.red && a.N == 12) return launch_sweep<MODE, G, false, 3, false, true, 12>(a, s);
-            if (!pat && !a.red && (a.N + 3) / 4 == 3) return launch_sweep<MODE, G, false, 3, false, true>(a, s);
-        }
-        if (a.red) return pat ? launch_sweep<MODE, G, true, 0, true, true>(a, s) : launch_sweep<MODE, G, false, 0, true, true>(a, s);
-        return pat ? launch_sweep<MODE, G, true, 0, false, true>(a, s) : launch_sweep<MODE, G, false, 0, false, true>(a, s);
-    }
-}
-
-// Replica exchange (never a default, not a mode of the reference): the run-time probe loop for every size, plus the two
-// single_N shapes of BASELINE (board N = 12 at 4 lanes, full_3d N = 12 at 8) with their unrolled steps.
-template <int MODE, int G>
-int launch_sweep_exchange(const KArgs& a, hipStream_t s) {
-    if (a.rng == MCQ_RNG_PHILOX4X32_10) return launch_sweep<MODE, G, false, 0, false, true, 0, true>(a, s);
-    if constexpr (MODE == MCQ_MODE_BOARD && G == 4) {
-        if (a.N == 12) return launch_sweep<MODE, G, false, 3, false, false, 12, true>(a, s);
-    }
-    if constexpr (MODE == MCQ_MODE_FULL3D && G == 8) {
-        if (a.N == 12 && a.Q == 144) {
-            KArgs b = a;
-            b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q);
-            return launch_sweep<MODE, G, false, 3, false, false, 12, true>(b, s);
-        }
-    }
-    return launch_sweep<MODE, G, false, 0, false, false, 0, true>(a, s);
-}
-
-template <int MODE, int G>
-int launch_sweep_g(const KArgs& a, hipStream_t s) {
-    if (a.exch_every > 0) return launch_sweep_exchange<MODE, G>(a, s);
-    if (a.rng == MCQ_RNG_PHILOX4X32_10) return launch_sweep_philox<MODE, G>(a, s);
-    if constexpr (MODE == MCQ_MODE_FULL3D) {  // no early stop (experiments.py:199-279)
-        if (a.N > 32) {  // 64-bit column words (validate(): 16 lanes per chain, NumPy's stream, no exchange)
-            if constexpr (G == 16) {
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, false, a.Q, false, false, true);
-                return a.red ? launch_sweep<MODE, G, false, 0, true, false, 0, false, false, false, false, false, true>(b, s)
-                             : launch_sweep<MODE, G, false, 0, false, false, 0, false, false, false, false, false, true>(b, s);
-            } else {
-                return fail(MCQ_EINVAL, "full_3d beyond N = 32 runs at 16 lanes per chain");
-            }
-        }
-        if constexpr (G == 8) {  // N <= 16: 16-bit column words, four lanes around each of the two cells
-            const int nt = (a.N + 3) / 4;
-            if (a.red && nt == 3) {  // BASELINE config 3's shape with the reduced trace
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q);
-                return a.N == 12 && a.Q == 144 ? launch_sweep<MODE, G, false, 3, true, false, 12>(b, s) : launch_sweep<MODE, G, false, 3, true>(b, s);
-            }
-            if (!a.red && nt <= 4) {
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q);
-                switch (nt) {
-                case 1: return launch_sweep<MODE, G, false, 1, false>(b, s);
-                case 2: return launch_sweep<MODE, G, false, 2, false>(b, s);
-                case 3: return a.N == 12 && a.Q == 144 ? launch_sweep<MODE, G, false, 3, false, false, 12>(b, s) : launch_sweep<MODE, G, false, 3, false>(b, s);
-                default: return launch_sweep<MODE, G, false, 4, false>(b, s);
-                }
-            }
-        }
-        if constexpr (G == 4) {
-            // the slim layout (N = 9..12): two lanes around each of the two cells, ceil(N / 2) unrolled passes, the queens in global memory.
-            // (65 536 chains x 20 000 steps against 8 lanes: N = 9 53.2 / 65.4 ms, N = 10 49.6 / 62.6, N = 11 60.3 / 62.9, N = 12 52.1 / 59.8;
-            // seven and eight passes spill and lose -- N = 13 129 / 68 ms, N = 16 109 / 91: profiles/r04_full3d_slim.txt)
-            if (a.N > 8 && a.N <= 12) {
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_FULL3D, true, a.Q, true);
-                if (a.red) {  // the reduced trace (what the drivers' statistics runs take)
-                    if ((a.N + 1) / 2 == 5) return launch_sweep<MODE, G, false, 5, true, false, 0, false, false, false, true>(b, s);
-                    return a.N == 12 && a.Q == 144 ? launch_sweep<MODE, G, false, 6, true, false, 12, false, false, false, true>(b, s)
-                                                   : launch_sweep<MODE, G, false, 6, true, false, 0, false, false, false, true>(b, s);
-                }
-                if ((a.N + 1) / 2 == 5) return launch_sweep<MODE, G, false, 5, false, false, 0, false, false, false, true>(b, s);
-                return a.N == 12 && a.Q == 144 ? launch_sweep<MODE, G, false, 6, false, false, 12, false, false, false, true>(b, s)
-                                               : launch_sweep<MODE, G, false, 6, false, false, 0, false, false, false, true>(b, s);
-            }
-        }
-        return a.red ? launch_sweep<MODE, G, false, 0, true>(a, s) : launch_sweep<MODE, G, false, 0, false>(a, s);
-    } else {
-        const bool pat = a.patience >= 0 && a.patience <= a.n_steps;  // a patience beyond n_steps can never stop a chain: the plain variants give the same results
-        if constexpr (G == 2) {  // 32 chains per wavefront, ceil(N / 2) packed probe passes: the size of BASELINE config 2
-            if (a.N == 12) {
-                if (!pat) return a.red ? launch_sweep<MODE, G, false, 6, true, false, 12>(a, s) : launch_sweep<MODE, G, false, 6, false, false, 12>(a, s);
-                if (!a.red) return launch_sweep<MODE, G, true, 6, false, false, 12>(a, s);
-            }
-            // the other sizes up to N = 12 without early stop and with a full trace or none: what a job list takes for its SHORT launches when it
-            // balances the lanes of launches that run side by side (half the wavefronts of 4 lanes, a longer step: jobs.plan_lanes)
-            if (!pat && !a.red && a.N <= 12) {
-                if (a.N <= 4) return launch_sweep<MODE, G, false, 2, false, false, 0, false, true>(a, s);  // (five candidates for new_k, like the 4-lane kernels of N <= 5)
-                if (a.N == 5) return launch_sweep<MODE, G, false, 3, false, false, 0, false, true>(a, s);
-                switch ((a.N + 1) / 2) {
-                case 3: return launch_sweep<MODE, G, false, 3, false>(a, s);
-                case 4: return launch_sweep<MODE, G, false, 4, false>(a, s);
-                case 5: return launch_sweep<MODE, G, false, 5, false>(a, s);
-                default: return launch_sweep<MODE, G, false, 6, false>(a, s);
-                }
-            }
-        }
-        if constexpr (G == 4) {
-            // dE from line counters (MCQ_FLAG_LINE_COUNTERS; N <= 8, NumPy's stream, plain or early-stop, full or no trace): see CNT at the kernel
-            if ((a.flags & MCQ_FLAG_LINE_COUNTERS) && a.N <= 8 && !a.red) {
-                KArgs b = a;
-                b.chain_lds_words = chain_lds_words_for(a.N, MCQ_MODE_BOARD, false, 0, false, true);
-                if (a.N <= 5) return pat ? launch_sweep<MODE, G, true, 0, false, false, 0, false, true, false, false, true>(b, s) : launch_sweep<MODE, G, false, 0, false, false, 0, false, true, false, false, true>(b, s);
-                return pat ? launch_sweep<MODE, G, true, 0, false, false, 0, false, false, false, false, true>(b, s) : launch_sweep<MODE, G, false, 0, false, false, 0, false, false, false, false, true>(b, s);
-            }
-        }
-        if constexpr (G == 4) {  // straight-line probe blocks for the common board sizes
-            // (early stopping -- the reference's default early_stop_patience = 100000 -- has its own unrolled variants for the
-            // sizes that default to 4 lanes)
-            if (pat && !a.red && a.N <= 5)  // (five candidates for new_k, like the plain variants below)
-                return a.N <= 4 ? launch_sweep<MODE, G, true, 1, false, false, 0, false, true>(a, s) : launch_sweep<MODE, G, true, 2, false, false, 0, false, true>(a, s);
-            if (pat && !a.red) switch ((a.N + G - 1) / G) {
-                case 1: return launch_sweep<MODE, G, true, 1, false>(a, s);
-                case 2: return launch_sweep<MODE, G, true, 2, false>(a, s);
-                case 3: return a.N == 12 ? launch_sweep<MODE, G, true, 3, false, false, 12>(a, s) : launch_sweep<MODE, G, true, 3, false>(a, s);
-                default: break;
-                }
-            if (!pat && !a.red && a.N <= 5)  // five candidates for new_k: the small cells of measure_min_energy_vs_N (BASELINE config 4)
-                return a.N <= 4 ? launch_sweep<MODE, G, false, 1, false, false, 0, false, true>(a, s) : launch_sweep<MODE, G, false, 2, false, false, 0, false, true>(a, s);
-            if (!pat && a.N == 12)  // the size of BASELINE config 2: N as a compile-time constant
-                return a.red ? launch_sweep<MODE, G, false, 3, true, false, 12>(a, s) : launch_sweep<MODE, G, false, 3, false, false, 12>(a, s);
-            // the long cells of measure_min_energy_vs_N (BASELINE configs[3]): N as a compile-time constant (125 / 119 / 118 VGPRs and 10 / 7 / 4
-            // spilled SGPRs against 128 / 40 of the generic five-pass variant; N = 19 is left out: its instantiation spills 324 VGPRs)
-            if (!pat && !a.red && (a.N == 17 || a.N == 18 || a.N == 20)) switch (a.N) {
-                case 17: return launch_sweep<MODE, G, false, 5, false, false, 17>(a, s);
-                case 18: return launch_sweep<MODE, G, false, 5, false, false, 18>(a, s);
-                default: return launch_sweep<MODE, G, false, 5, false, false, 20>(a, s);
-                }
-            if (!pat) switch ((a.N + G - 1) / G) {
-#define MCQ_NT_CASE(nt) case nt: return a.red ? launch_sweep<MODE, G, false, (nt >= 4 ? 0 : nt), true>(a, s) : launch_sweep<MODE, G, false, nt, false>(a, s)
-                MCQ_NT_CASE(1);  // N = 2..4
-                MCQ_NT_CASE(2);  // N = 5..8
-                MCQ_NT_CASE(3);  // N = 9..12
-                MCQ_NT_CASE(4);  // N = 13..16 (up to here: packed 16-bit masks); from four passes on the reduced-trace variants would spill and take the loop
-                MCQ_NT_CASE(5);  // N = 17..20
-                MCQ_NT_CASE(6);  // N = 21..24
-#undef MCQ_NT_CASE
-                default: break;
-                }
-        }
-        if constexpr (G == 8) {  // larger boards run 8 lanes per chain by default: 3 or 4 straight-line probe passes
-            // (a launch that leaves the device at most half full -- two wavefronts per SIMD -- takes the variants that request the probe
-            // heights early: see EARLY_PROBES in the kernel)
-            const bool roomy = (a.n_chains + 7) / 8 <= 2LL * device_simds();
-            if (!pat && a.red && a.N == 24)  // BASELINE config 5: the beta-pair driver's shape (N = 24, reduced trace)
-                return roomy ? launch_sweep<MODE, G, false, 3, true, false, 24, false, false, true>(a, s) : launch_sweep<MODE, G, false, 3, true, false, 24>(a, s);
-            if (!pat && a.red && a.N > 16 && a.N <= 24) return roomy ? launch_sweep<MODE, G, false, 3, true, false, 0, false, false, true>(a, s) : launch_sweep<MODE, G, false, 3, true>(a, s);
-            if (!pat && a.red && a.N > 8 && a.N <= 16) return launch_sweep<MODE, G, false, 2, true>(a, s);
-            if (!pat && !a.red && a.N > 16 && a.N <= 24) return roomy ? launch_sweep<MODE, G, false, 3, false, false, 0, false, false, true>(a, s) : launch_sweep<MODE, G, false, 3, false>(a, s);
-            if (!pat && !a.red && a.N > 24 && a.N <= 32) return launch_sweep<MODE, G, false, 4, false>(a, s);
-            if (!pat && !a.red && a.N > 8 && a.N <= 16) return launch_sweep<MODE, G, false, 2, false>(a, s);  // N = 9..16: two packed passes
-            if (pat && !a.red && a.N > 16 && a.N <= 24) return roomy ? launch_sweep<MODE, G, true, 3, false, false, 0, false, false, true>(a, s) : launch_sweep<MODE, G, true, 3, false>(a, s);
-            if (pat && !a.red && a.N > 24 && a.N <= 32) return launch_sweep<MODE, G, true, 4, false>(a, s);
-            if (pat && !a.red && a.N > 8 && a.N <= 16) return launch_sweep<MODE, G, true, 2, false>(a, s);
-        }
-        if constexpr (G == 16) {  // 4 chains per wavefront: one packed probe pass up to N = 16, two unpacked ones up to N = 32
-            // (what a launch far below the device's capacity takes -- 16 384 chains of N = 24, the per-GPU shape of BASELINE configs[4], are
-            // four wavefronts per SIMD this way; before round 4 these widths ran the run-time probe loop)
-            const bool roomy = (a.n_chains + 3) / 4 <= 2LL * device_simds();
-            if (!pat && a.N <= 16) return a.red ? launch_sweep<MODE, G, false, 1, true>(a, s) : launch_sweep<MODE, G, false, 1, false>(a, s);
-            if (!pat && a.red && a.N == 24) return launch_sweep<MODE, G, false, 2, true, false, 24>(a, s);
-            if (!pat && a.N <= 32) {
-                if (a.red) return launch_sweep<MODE, G, false, 2, true>(a, s);
-                return roomy ? launch_sweep<MODE, G, false, 2, false, false, 0, false, false, true>(a, s) : launch_sweep<MODE, G, false, 2, false>(a, s);
-            }
-        }
-        if (a.red) return pat ? launch_sweep<MODE, G, true, 0, true>(a, s) : launch_sweep<MODE, G, false, 0, true>(a, s);
-        return pat ? launch_sweep<MODE, G, true, 0, false>(a, s) : launch_sweep<MODE, G, false, 0, false>(a, s);
-    }
-}
-
-template <int MODE>
-int launch_sweep_mode(const KArgs& a, int G, hipStream_t s) {
-    if (G == 2) {
-        if constexpr (MODE == MCQ_MODE_BOARD) return launch_sweep_g<MODE, 2>(a, s);
-        else return fail(MCQ_EINVAL, "lanes_per_chain 2 applies to mcmc_type board");
-    }
-    if (G == 4) return launch_sweep_g<MODE, 4>(a, s);
-    if (G == 8) return launch_sweep_g<MODE, 8>(a, s);
-    return launch_sweep_g<MODE, 16>(a, s);
 }
 
 int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_outputs* out, void* workspace,
@@ -2614,13 +2737,10 @@ int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_output
     if (rc != MCQ_OK) return rc;
     if (from) a.step0 = from->first_step, a.sched_steps = from->schedule_steps;  // (a beta_table covers this call's steps only)
 
-    const int G = effective_lanes(p);
-    {  // the variant this launch takes must fit the LDS: found out before anything is enqueued
-        KArgs d = a;
-        d.dry = 1;
-        rc = p->mode == MCQ_MODE_BOARD ? launch_sweep_mode<MCQ_MODE_BOARD>(d, G, s) : launch_sweep_mode<MCQ_MODE_FULL3D>(d, G, s);
-        if (rc != MCQ_OK) return rc;
-    }
+    // the variant this launch takes, and that it fits the LDS: found out before anything is enqueued
+    SweepPlan sweep;
+    rc = plan_sweep(p, &sweep);
+    if (rc != MCQ_OK) return rc;
     if (a.out.accept_bits)  // chains that stop early leave their later words untouched
         HIP_TRY(hipMemsetAsync(a.out.accept_bits, 0, (size_t)p->n_chains * p->bits_stride * 8, s));
 
@@ -2674,17 +2794,9 @@ int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_output
     auto launch_init_part = [&](const KArgs& k, long long count) -> hipError_t {  // chains k.chain0 .. k.chain0 + count - 1
         const size_t bytes = (size_t)init_ci * init_lds;
         const unsigned grid = (unsigned)((count + init_ci - 1) / init_ci);
-        hipError_t e;
-        if (init_ci == 4) {
-            e = hipFuncSetAttribute((const void*)mcq_init_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e == hipSuccess) hipLaunchKernelGGL(mcq_init_kernel<4>, dim3(grid), dim3(64), bytes, s, k);
-        } else if (init_ci == 2) {
-            e = hipFuncSetAttribute((const void*)mcq_init_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e == hipSuccess) hipLaunchKernelGGL(mcq_init_kernel<2>, dim3(grid), dim3(64), bytes, s, k);
-        } else {
-            e = hipFuncSetAttribute((const void*)mcq_init_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e == hipSuccess) hipLaunchKernelGGL(mcq_init_kernel<1>, dim3(grid), dim3(64), bytes, s, k);
-        }
+        void (*const kernel)(KArgs) = init_ci == 4 ? &mcq_init_kernel<4> : init_ci == 2 ? &mcq_init_kernel<2> : &mcq_init_kernel<1>;
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e == hipSuccess) hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), bytes, s, k);
         return e;
     };
     auto launch_init = [&](const KArgs& k0) -> hipError_t {
@@ -2726,13 +2838,7 @@ int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_output
             for (size_t t = 0; t < n_sets_of(p); t++) {
                 KArgs b = a;
                 b.init = p->sets[t].init_plus1 ? p->sets[t].init_plus1 - 1 : p->init;
-                b.klarner_M = 0;
-                if (b.init == MCQ_INIT_KLARNER && gcd_int(p->N, 210) != 1)
-                    for (int m = p->N - 1; m > 0; m--)
-                        if (gcd_int(m, 210) == 1) {
-                            b.klarner_M = m;
-                            break;
-                        }
+                b.klarner_M = klarner_core(b.init, p->N);
                 b.seeds = a.seeds + t * (size_t)p->chains_per_set;
                 b.ws = a.ws + t * (size_t)p->chains_per_set * a.rec_words;
                 if (a.qtab) b.qtab = a.qtab + t * (size_t)p->chains_per_set * a.qtab_stride * (p->N > 32 ? 2 : 1);
@@ -2746,7 +2852,7 @@ int run_device_impl(const mcq_params* p, const uint32_t* seeds, const mcq_output
     HIP_TRY(hipGetLastError());
     if (ev) HIP_TRY(hipEventRecord(ev[1], s));
 
-    rc = p->mode == MCQ_MODE_BOARD ? launch_sweep_mode<MCQ_MODE_BOARD>(a, G, s) : launch_sweep_mode<MCQ_MODE_FULL3D>(a, G, s);
+    rc = launch_sweep(sweep, a, s);
     if (rc != MCQ_OK) return rc;
     if (out->stream_words && p->rng == MCQ_RNG_MT19937_NUMPY) {
         hipLaunchKernelGGL(mcq_stream_words_kernel, dim3((unsigned)((p->n_chains + 255) / 256)), dim3(256), 0, s, out->stream_words, a.ws, a.rec_words, (long long)p->n_chains);
@@ -2789,6 +2895,20 @@ int32_t mcq_effective_lanes(const mcq_params* p) { return validate(p) == MCQ_OK 
 void mcq_stream_layout(const uint32_t* numpy_state, uint32_t* out) { stream_layout(numpy_state, out); }
 
 int32_t mcq_device_simds(void) { return device_simds(); }
+
+int mcq_sweep_variant(const mcq_params* p, int32_t variant[13], int64_t* lds_bytes) {
+    int rc = validate(p);
+    if (rc != MCQ_OK) return rc;
+    if (!variant || !lds_bytes) return fail(MCQ_EINVAL, "null argument");
+    SweepPlan plan;
+    rc = plan_sweep(p, &plan);
+    if (rc != MCQ_OK) return rc;
+    const SweepVariant& v = plan.v;
+    const int32_t values[13] = {v.mode, v.g, v.patience, v.nt, v.reduced, v.philox, v.nc, v.exch, v.cand5, v.earlyu, v.slim, v.cnt, v.wide};
+    memcpy(variant, values, sizeof values);
+    *lds_bytes = (int64_t)plan.lds_bytes;
+    return MCQ_OK;
+}
 
 size_t mcq_state_bytes(int32_t N, int32_t mode) {
     if (N < MCQ_MIN_N || N > (mode == MCQ_MODE_BOARD ? MCQ_MAX_N_BOARD : MCQ_MAX_N)) return 0;
