@@ -438,6 +438,48 @@ int mcq_resample_device(const mcq_resample* r, void* scratch, size_t scratch_byt
  * is ignored.  Equal to the plan kernel bit for bit; exported for the tests the way mcq_stream_layout is. */
 int mcq_resample_plan_host(const mcq_resample* r);
 
+/*
+ * Quench: the deterministic zero-temperature descent of board placements to a local minimum under single-height moves
+ * (csrc/mcq_quench.hip) -- NOT a mode of the reference, which ships the ingredient (State3DQueensBoard.conflicts_for_position,
+ * mcmc_board.py:147-193) and never uses it; never a default.  It certifies a placement as a local minimum, recounts its energy on the
+ * device independently of the sweep, and hands back the per-column conflict map.  Boards only.  The rule is integer-exact:
+ *   1. every input byte is clamped to N - 1 first (as the restore kernel of mcq_run_device_from does).
+ *   2. for a board of heights h[i][j], a column c = (i, j) and a height k, a(c, k) = the number of OTHER columns c' = (i', j') with
+ *        di = 0 or dj = 0 or |di| = |dj|     (di = i' - i, dj = j' - j: same row, same column or a diagonal of the board), and
+ *        |h(c') - k| = 0 or d,  d = max(|di|, |dj|)
+ *      -- conflicts_for_position(i, j, k).  The energy is E = 1/2 sum_c a(c, h(c)) (_compute_energy, mcmc_board.py:82-122).
+ *   3. one PASS visits the columns in row-major order.  For column c: k* = the SMALLEST k in 0 .. N - 1 with minimal a(c, k); if
+ *      a(c, k*) < a(c, h(c)) then h(c) = k*, E += a(c, k*) - a(c, h(c)), and one move is counted.  Later columns of the same pass see
+ *      the new height.
+ *   4. passes repeat until one makes no move (the placement is then a local minimum: no single column has a height with a lower
+ *      count) or max_passes passes have run (0 = no limit).  E falls by at least 1 per moving pass, so a run ends within
+ *      energy_in + 1 passes; n_passes counts the last, moveless pass too (a local minimum comes back with n_moves = 0, n_passes = 1).
+ * Chains do not interact, so state_out may be state_in.
+ */
+typedef struct mcq_quench {
+    int32_t N;            /* MCQ_MIN_N .. MCQ_MAX_N_BOARD */
+    int32_t mode;         /* MCQ_MODE_BOARD; full_3d is MCQ_EINVAL (a queen there has N^3 targets: a different design) */
+    int64_t n_chains;     /* 1 .. 2^31 - 1 */
+    int64_t max_passes;   /* >= 0; 0 = until a pass makes no move */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;   /* [n_chains][N*N]; may be state_in */
+    int32_t* energy_in;   /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;  /* optional [n_chains]: E of the output = energy_in + the sum of the moves' differences */
+    int32_t* n_moves;     /* optional [n_chains] */
+    int32_t* n_passes;    /* optional [n_chains] */
+    uint16_t* conflicts;  /* optional [n_chains][N*N]: a(c, h(c)) of the OUTPUT placement; its sum is 2 energy_out */
+} mcq_quench;
+
+/* the message of the last error of the calling thread from the two mcq_quench_* calls below (they do not set mcq_last_error()) */
+const char* mcq_quench_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`; asynchronous: nothing is copied back and nothing
+ * synchronises.  MCQ_EINVAL before any launch: mode other than board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative
+ * max_passes, a NULL state_in or state_out. */
+int mcq_quench_device(const mcq_quench* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output;
+ * exported for the tests the way mcq_resample_plan_host is. */
+int mcq_quench_host(const mcq_quench* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

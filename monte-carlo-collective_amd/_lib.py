@@ -180,6 +180,11 @@ def lib():
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
+        L.mcq_quench_last_error.restype = C.c_char_p
+        L.mcq_quench_device.restype = C.c_int
+        L.mcq_quench_device.argtypes = [C.POINTER(abi.Quench), C.c_void_p]
+        L.mcq_quench_host.restype = C.c_int
+        L.mcq_quench_host.argtypes = [C.POINTER(abi.Quench)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -207,6 +212,28 @@ def _check_population(rc):
     if rc == abi.ENOMEM:
         raise MemoryError(msg)
     raise McqError(msg)
+
+
+def _check_quench(rc):
+    """_check for the mcq_quench_* calls, which keep their own message (mcq_quench_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_quench_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def quench_host(q):
+    """mcq_quench_host on a filled abi.Quench block of HOST pointers.  Pure host code, no GPU."""
+    _check_quench(lib().mcq_quench_host(C.byref(q)))
+
+
+def quench_device(q, stream):
+    """mcq_quench_device on a filled abi.Quench block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_quench(lib().mcq_quench_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def resample_plan_host(energies, population, table, offsets):

@@ -143,6 +143,27 @@ def resample_table(dbeta):
     return np.ascontiguousarray(t[: int(zero[0]) + 1] if len(zero) else t)
 
 
+class Quench(C.Structure):
+    """include/mcq.h: mcq_quench -- the zero-temperature descent of board placements to a local minimum"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("max_passes", C.c_int64),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_passes", C.c_void_p),
+        ("conflicts", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a quench besides the placements: field -> dtype ("conflicts" has a row of N*N per chain)
+QUENCH_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.int32, "n_passes": np.int32, "conflicts": np.uint16}
+
+
 class PackSlot(C.Structure):
     """include/mcq.h: mcq_pack_slot -- where one job's fields sit in the packed summary tensor (word offsets, -1 = absent)"""
     _fields_ = [("counters", C.c_int64), ("min_slot", C.c_int64), ("best", C.c_int64), ("stb", C.c_int64), ("stats", C.c_int64)]

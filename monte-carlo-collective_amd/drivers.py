@@ -244,36 +244,53 @@ def write_best_heights(heights, N, path):
 
 
 def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.0, base_seed=42, init_mode="random",
-                    out_dir="competition_results", runner=None, timestamp=None, resample_every=None, population=None, resample_seed=0):
+                    out_dir="competition_results", runner=None, timestamp=None, resample_every=None, population=None, resample_seed=0, quench=False):
     """competition.py:143-187: board chains with linear annealing beta_start -> beta_end, seeds base_seed + r; the board
     of the run with the lowest best energy is written to {out_dir}/best_heights_{N}_{timestamp}.txt.
     Returns (best energy, heights, path).
 
     resample_every (not in the reference; None = the reference's independent chains, exactly as without the argument): the runs are
     the slots of a population annealing (population.anneal_population) resampled every that many steps inside populations of
-    `population` chains (None: all runs) with the offset words of `resample_seed`; `runner` is then unused."""
+    `population` chains (None: all runs) with the offset words of `resample_seed`; `runner` is then unused.
+
+    quench=True (not in the reference; off by default, and nothing changes when off): the best placement of every run is quenched to a
+    local minimum under single-height moves on the device (quench.py), and the board written is the one with the lowest QUENCHED energy
+    over the runs (the first such run).  The call then returns FOUR values, (quenched energy, heights, path, info), with
+    info = {"quenched": True, "run": r, "energy_before": that run's best_energy, "moves": the heights the quench changed}; the file
+    keeps the reference's format and has `_quenched` in its name."""
     sp = {"type": "linear_annealing", "beta_start": beta_start, "beta_end": beta_end}
     if resample_every is not None:
         from . import population as _pop
 
         res, _ = _pop.anneal_population(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), resample_every, population=population,
-                                        resample_seed=resample_seed, mcmc_type="board", trace=False, states=True)
-        return _write_competition(res, N, out_dir, timestamp)
+                                        resample_seed=resample_seed, mcmc_type="board", trace=False, states=True, quench=quench)
+        return _write_competition(res, N, out_dir, timestamp, quench)
     runner = _runner_or_default(runner)
     try:
         res, _ = runner(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), mcmc_type="board", early_stop_patience=None,
                         trace=False, states=True)
     except TypeError:  # injected runners without a `states` argument return the states anyway
         res, _ = runner(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), mcmc_type="board", early_stop_patience=None, trace=False)
-    return _write_competition(res, N, out_dir, timestamp)
+    return _write_competition(res, N, out_dir, timestamp, quench)
 
 
-def _write_competition(res, N, out_dir, timestamp):
+def _write_competition(res, N, out_dir, timestamp, quench=False):
     import time
 
+    stamp = timestamp if timestamp is not None else time.strftime("%Y%m%d_%H%M%S")
+    if quench:
+        if "quenched_state" not in res:  # independent chains: their best placements go through the quench here
+            from . import quench as _quench
+
+            q = _quench.quench_states(N, np.asarray(res["best_state"]), conflicts=False)
+            res = dict(res, quenched_state=q["state"], quenched_energy=q["energy_out"], quench_moves=q["n_moves"])
+        r = int(np.argmin(res["quenched_energy"]))
+        heights = np.asarray(res["quenched_state"][r]).reshape(N, N)
+        path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}_quenched.txt"))
+        info = {"quenched": True, "run": r, "energy_before": int(res["best_energy"][r]), "moves": int(res["quench_moves"][r])}
+        return int(res["quenched_energy"][r]), heights, path, info
     r = int(np.argmin(res["best_energy"]))  # first run with the minimum, like min() over the runs in order
     heights = np.asarray(res["best_state"][r]).reshape(N, N)
-    stamp = timestamp if timestamp is not None else time.strftime("%Y%m%d_%H%M%S")
     path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}.txt"))
     return int(res["best_energy"][r]), heights, path
 

@@ -440,11 +440,14 @@ def _run_experiment_segments(N, n_steps, init_mode, schedule_params, seeds, mcmc
 
 
 def run_population(N, n_steps, init_mode, beta_schedule, n_runs, resample_every, population=None, resample_seed=0, base_seed=0, verbose=False,
-                   schedule_params=None, mcmc_type="full_3d", return_steps=True, lanes_per_chain=0):
+                   schedule_params=None, mcmc_type="full_3d", return_steps=True, lanes_per_chain=0, quench=False):
     """run_experiment's 6-tuple over population annealing (population.anneal_population; not in the reference): the n_runs chains, seeded
     base_seed + r, are resampled every `resample_every` steps inside populations of `population` chains (None: one population of all).
     Run r of the result is SLOT r: its history is the slot's own, joined the way run_experiment(segment_steps=) joins segments, so it
-    may jump at a boundary where the slot took over a parent's placement.  There is no early stopping: it cannot be carried across segments."""
+    may jump at a boundary where the slot took over a parent's placement.  There is no early stopping: it cannot be carried across segments.
+    quench=True (boards only; off by default): every slot's best placement is quenched to a local minimum on the device behind the run
+    (population.anneal_population(quench=True)) and the tuple gains a SEVENTH element, a dict of `quenched_state`, `quenched_energy` and
+    `quench_moves`; the six elements before it are what the call without it returns."""
     from . import population as _pop
 
     if n_runs <= 0:
@@ -453,7 +456,7 @@ def run_population(N, n_steps, init_mode, beta_schedule, n_runs, resample_every,
     seeds = abi.seeds_for(base_seed, n_runs)
     timings = {}
     res, _ = _pop.anneal_population(N, n_steps, init_mode, sp, seeds, resample_every, population=population, resample_seed=resample_seed,
-                                    mcmc_type=mcmc_type, trace=True, states=False, lanes_per_chain=lanes_per_chain, timings=timings)
+                                    mcmc_type=mcmc_type, trace=True, states=False, lanes_per_chain=lanes_per_chain, timings=timings, quench=quench)
     all_histories = [res["energy_hist"][r, : int(n_steps) + 1] for r in range(n_runs)]
     best_energies = [int(b) for b in res["best_energy"]]
     if return_steps:
@@ -464,4 +467,7 @@ def run_population(N, n_steps, init_mode, beta_schedule, n_runs, resample_every,
     if verbose:
         for b in best_energies:
             print(b)
-    return all_histories, best_energies, [timings["run_seconds"] / n_runs] * n_runs, all_acc, all_rej, [int(s) for s in res["steps_to_best"]]
+    six = (all_histories, best_energies, [timings["run_seconds"] / n_runs] * n_runs, all_acc, all_rej, [int(s) for s in res["steps_to_best"]])
+    if quench:
+        return six + ({k: res[k] for k in ("quenched_state", "quenched_energy", "quench_moves")},)
+    return six

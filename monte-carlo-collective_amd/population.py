@@ -81,7 +81,7 @@ def ancestors_of(parents, n_chains):
 
 
 def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_every, population=None, resample_seed=0, mcmc_type="board",
-                      trace=False, states=True, lanes_per_chain=0, Q=None, timings=None):
+                      trace=False, states=True, lanes_per_chain=0, Q=None, timings=None, quench=False):
     """Every chain of `seeds` for n_steps steps, resampled every `resample_every` steps inside populations of `population` consecutive
     chains (None: all chains form one population).
 
@@ -99,7 +99,10 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
     ValueError before anything is launched (check, boundaries): a schedule that decreases over a segment, a resample_every <= 0, a
     population that does not divide the chains, is no multiple of 16 or exceeds 2^19, a full-trace segment row at the 2^24 limit.  The
     chains run NumPy's stream without early stopping or replica exchange; check() refuses a Params block that says otherwise.
-    `timings` (a dict, optional) receives wall seconds of the enqueue + wait."""
+    `timings` (a dict, optional) receives wall seconds of the enqueue + wait.
+    quench=True (boards only; off by default, and nothing changes when off): best_state of every slot is quenched to a local minimum
+    (quench.quench_device) on the same stream behind the last fold, with no host synchronisation before it; `res` gains `quenched_state`
+    uint8[n_chains][N*N], `quenched_energy` and `quench_moves` int32[n_chains].  Every other field is what the run without it returns."""
     import time
 
     import torch
@@ -110,6 +113,8 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
     seeds = seeds.astype(np.uint32)
     if isinstance(schedule_params, (list, tuple)):
         raise ValueError("population annealing runs one schedule: schedule sets are not resampled")
+    if quench and abi.mode_of(mcmc_type) != abi.MODE_BOARD:
+        raise ValueError("quench=True: the quench runs boards only (mcmc_type='board')")
     n = len(seeds)
     mk = lambda steps: abi.make_params(N, steps, init_mode, schedule_params, n, mcmc_type=mcmc_type, early_stop_patience=None, trace=trace,  # noqa: E731
                                        lanes_per_chain=lanes_per_chain, Q=Q)
@@ -187,6 +192,11 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
                 bits[:, done: done + L] = np.unpackbits(a, axis=1, bitorder="little")[:, :L]
             state = pop_state
             done += L
+        quenched = None
+        if quench:  # behind the last fold, which has written acc["best_state"]; same stream, nothing waited for
+            from . import quench as _quench
+
+            quenched = _quench.quench_device(N, acc["best_state"], conflicts=False, stream=st)
         t_wait = time.perf_counter()
         st.synchronize()
         t_end = time.perf_counter()
@@ -209,6 +219,9 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
     }
     if states:
         res["best_state"], res["final_state"] = acc["best_state"].cpu().numpy(), last["final_state"]
+    if quenched is not None:
+        res["quenched_state"], res["quenched_energy"] = quenched["state"].cpu().numpy(), quenched["energy_out"].cpu().numpy()
+        res["quench_moves"] = quenched["n_moves"].cpu().numpy()
     if reduced is not None:
         res.update({key: big.cpu().numpy() for key, big in reduced.items()})
     if hist is not None:

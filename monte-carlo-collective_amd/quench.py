@@ -1,0 +1,111 @@
+"""Quench: the deterministic zero-temperature descent of board placements to a local minimum (include/mcq.h: mcq_quench, where the rule
+is stated; csrc/mcq_quench.hip).
+
+NOT a mode of the reference -- it ships conflicts_for_position (mcmc_board.py:147-193) and never uses it --, never a default, and
+labelled as such like Philox, replica exchange and population annealing.  What a sweep hands back (best_state, final_state, the
+competition board) is whatever a thermal chain last held; the quench says whether that placement is a local minimum under
+single-height moves, what the minimum below it is, recounts its energy on the device independently of the sweep, and returns the
+per-column conflict map.  Boards only, N = 2 .. 128.
+"""
+import numpy as np
+
+from . import _lib, abi
+
+FIELDS = ("state", "energy_in", "energy_out", "n_moves", "n_passes", "conflicts")
+
+
+def _block(N, n, max_passes):
+    q = abi.Quench()
+    q.N, q.mode, q.n_chains, q.max_passes = int(N), abi.MODE_BOARD, int(n), int(max_passes)
+    return q
+
+
+def _host_states(N, states):
+    s = np.ascontiguousarray(states, dtype=np.uint8)
+    N = int(N)
+    if s.size == 0:
+        return s.reshape(0, max(N, 0) ** 2)
+    if s.ndim == 1 or s.shape == (N, N):  # one board
+        s = s.reshape(1, -1)
+    s = s.reshape(s.shape[0], -1)
+    if abi.MIN_N <= N <= abi.MAX_N_BOARD and s.shape[1] != N * N:
+        raise ValueError(f"states must be uint8[n_chains][{N * N}] (final_state layout of a board), got {s.shape}")
+    return s
+
+
+def quench_states_host(N, states, max_passes=0, conflicts=True):
+    """mcq_quench_host: the rule in the library's plain host code, NumPy in and out, no GPU.  Same result as quench_states."""
+    s = _host_states(N, states)
+    n = s.shape[0]
+    out = {"state": np.zeros_like(s)}
+    for k, dt in abi.QUENCH_DTYPES.items():
+        if k != "conflicts" or conflicts:
+            out[k] = np.zeros((n, s.shape[1]) if k == "conflicts" else n, dtype=dt)
+    q = _block(N, n, max_passes)
+    q.state_in, q.state_out = s.ctypes.data, out["state"].ctypes.data
+    for k in abi.QUENCH_DTYPES:
+        if k in out:
+            setattr(q, k, out[k].ctypes.data)
+    _lib.quench_host(q)
+    return out
+
+
+def quench_device(N, states, max_passes=0, out=None, conflicts=True, stream=None):
+    """mcq_quench_device on a torch uint8 tensor [n_chains][N*N] of the current device (e.g. DeviceRun.t["best_state"]), enqueued on
+    `stream` (default: torch's current stream).  Asynchronous: nothing is copied back and nothing synchronises, so the results are valid
+    once the stream has passed the call.  `out` (optional) is the tensor the placements go to; it may be `states` itself (in place),
+    default a new one.  Returns a dict of tensors: `state` uint8 like `states`, `energy_in` (the recount of the input), `energy_out`,
+    `n_moves`, `n_passes` int32[n_chains] and, unless conflicts=False, `conflicts` int16[n_chains][N*N] (the uint16 counts a(c, h(c)) of the
+    output; at most 4 (N - 1), so the sign bit is never set)."""
+    import torch
+
+    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
+        raise ValueError("quench_device takes a contiguous uint8 tensor on the GPU")
+    n = int(states.shape[0]) if states.dim() == 2 else 0
+    if states.dim() != 2 or (abi.MIN_N <= int(N) <= abi.MAX_N_BOARD and int(states.shape[1]) != int(N) * int(N)):
+        raise ValueError(f"states must be uint8[n_chains][{int(N) * int(N)}] (final_state layout of a board), got {tuple(states.shape)}")
+    dev = states.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        if out is None:
+            out = torch.empty_like(states)
+        elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
+        res = {"state": out}
+        for k in ("energy_in", "energy_out", "n_moves", "n_passes"):
+            res[k] = torch.empty(n, dtype=torch.int32, device=dev)
+        if conflicts:
+            res["conflicts"] = torch.empty(tuple(states.shape), dtype=torch.int16, device=dev)
+        q = _block(N, n, max_passes)
+        q.state_in, q.state_out = states.data_ptr(), out.data_ptr()
+        for k in abi.QUENCH_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.quench_device(q, st)
+    return res
+
+
+def quench_states(N, states, max_passes=0, conflicts=True):
+    """Quench board placements on the GPU: `states` is uint8[n_chains][N*N] (the final_state / best_state layout; one board of N*N
+    heights is taken as one chain), bytes >= N are clamped to N - 1.  max_passes = 0 runs until a pass makes no move.  Returns a dict of
+    NumPy arrays: `state` (the placements after the descent), `energy_in` (the energy of the input, recounted on the device),
+    `energy_out`, `n_moves`, `n_passes` int32[n_chains], and `conflicts` uint16[n_chains][N*N], the number of queens attacking each
+    column's queen in the output (its sum is 2 energy_out).  A placement with n_moves == 0 was a local minimum already.
+    ValueError for what the library refuses (N outside 2 .. 128, no chain, a negative max_passes)."""
+    import torch
+
+    s = _host_states(N, states)
+    if s.shape[0] == 0:
+        _lib.quench_host(_block(N, 0, max_passes))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = quench_device(N, torch.from_numpy(s).to(dev), max_passes=max_passes, conflicts=conflicts)
+    torch.cuda.current_stream(dev).synchronize()
+    return to_numpy(res)
+
+
+def to_numpy(res):
+    """The dict quench_device returned, as NumPy arrays (conflicts as uint16).  The stream must have passed the call."""
+    out = {k: t.cpu().numpy() for k, t in res.items()}
+    if "conflicts" in out:
+        out["conflicts"] = out["conflicts"].view(np.uint16)
+    return out

@@ -256,6 +256,52 @@ def run_stream_chain(job):
     return res
 
 
+def gen_conflicts(ref_path, out):
+    """State3DQueensBoard.conflicts_for_position (mcmc_board.py:147-193) for EVERY cell (i, j, k) of ~30 boards, and _compute_energy of each:
+    what the quench (include/mcq.h: mcq_quench) is pinned by.  Random, latin and klarner boards and end states of the golden board chains.
+    conflicts.npz holds data only -- per board b: b_heights uint8[N*N], b_table uint8[N*N][N] (a count is at most 4 (N - 1) <= 252 here),
+    b_energy -- and its own list of cases (`cases`, JSON): the manifest is left alone.  `python tools/gen_golden.py --only conflicts`."""
+    import contextlib
+    import io
+
+    _ref(ref_path)
+    from mcmc_board import State3DQueensBoard
+
+    boards = []
+    for N in (2, 3, 5, 8, 12, 13, 16, 17, 24, 32, 33, 64):
+        np.random.seed(900 + N)
+        boards.append((f"random N={N}", N, State3DQueensBoard(N, init_mode="random").heights))
+    for N in (5, 8, 12, 17):
+        boards.append((f"latin N={N}", N, State3DQueensBoard(N, init_mode="latin").heights))
+    for N in (11, 12, 13, 17):  # 12: gcd(12, 210) != 1, the block of M = 11 and random heights around it
+        np.random.seed(950 + N)
+        with contextlib.redirect_stdout(io.StringIO()):
+            boards.append((f"klarner N={N}", N, State3DQueensBoard(N, init_mode="klarner").heights))
+    with open(os.path.join(out, "manifest.json")) as f:
+        manifest = json.load(f)
+    picked = {"chains": {3: 1, 6: 2, 12: 3, 17: 1, 24: 1}, "chains_big": {33: 1, 64: 1}}
+    for name, want in picked.items():
+        z = np.load(os.path.join(out, name + ".npz"))
+        left = dict(want)
+        for c in manifest[name]:
+            if c["mode"] == "board" and left.get(c["N"], 0) > 0 and c["n_steps"] >= 150:
+                left[c["N"]] -= 1
+                boards.append((f"final state of {name} {c['key']}", c["N"], z[f"{c['key']}_final_state"].reshape(c["N"], c["N"])))
+    arrays, cases = {}, []
+    for b, (what, N, heights) in enumerate(boards):
+        st = State3DQueensBoard(N, heights=np.asarray(heights, dtype=int))
+        tab = np.array([[[st.conflicts_for_position(i, j, k) for k in range(N)] for j in range(N)] for i in range(N)])
+        assert tab.max() <= 255
+        key = f"b{b:02d}"
+        arrays[key + "_heights"] = np.asarray(st.heights, dtype=np.uint8).reshape(-1)
+        arrays[key + "_table"] = tab.astype(np.uint8).reshape(N * N, N)
+        arrays[key + "_energy"] = np.int64(st.energy(recompute=True))
+        cases.append({"key": key, "what": what, "N": N})
+    arrays["cases"] = np.array(json.dumps(cases))
+    np.savez_compressed(os.path.join(out, "conflicts.npz"), **arrays)
+    return cases
+
+
 def gen_beta(ref_path, out):
     """F5: float64 beta(step) tables of the five schedule closures."""
     ex = _ref(ref_path)
@@ -352,9 +398,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
     ap.add_argument("--workers", type=int, default=8)
-    ap.add_argument("--only", default="", help="'q': only the Q != N^2 chains (chains_q.npz); 'big': only the boards beyond N = 32 (chains_big.npz); 'wide': only the full_3d chains beyond N = 32 (chains_wide.npz); 'stream': only the seed=None chains (chains_stream.npz); merged into the existing manifest")
+    ap.add_argument("--only", default="", help="'q': only the Q != N^2 chains (chains_q.npz); 'big': only the boards beyond N = 32 (chains_big.npz); 'wide': only the full_3d chains beyond N = 32 (chains_wide.npz); 'stream': only the seed=None chains (chains_stream.npz); merged into the existing manifest.  'conflicts': only conflicts.npz, the conflict tables the quench is pinned by (the manifest is left alone)")
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
+    if args.only == "conflicts":
+        cases = gen_conflicts(args.reference, OUT)
+        print(f"wrote {len(cases)} boards to conflicts.npz ({os.path.getsize(os.path.join(OUT, 'conflicts.npz'))} bytes)")
+        return
     if args.only in ("q", "big", "wide", "stream"):
         name = "chains_" + args.only
         cases = {"q": q_cases, "big": big_cases, "wide": wide_cases, "stream": stream_cases}[args.only]()
