@@ -480,6 +480,67 @@ int mcq_quench_device(const mcq_quench* q, void* hip_stream);
  * exported for the tests the way mcq_resample_plan_host is. */
 int mcq_quench_host(const mcq_quench* q);
 
+/*
+ * Heat-bath column sweeps of board placements (csrc/mcq_heatbath.hip) -- NOT a mode of the reference, whose only move is one random
+ * column, one random height and one Metropolis test (its report lists better moves as future work); never a default, like Philox,
+ * replica exchange, population annealing and the quench.  A column's new height is DRAWN from the Boltzmann weights of all N heights
+ * at once, so no proposal is rejected.  Boards only.  The rule is integer-exact:
+ *   1. every input byte is clamped to N - 1 first; a(c, k) and E are those of the quench rule above, items 1 - 2.
+ *   2. a call runs n_sweeps sweeps; sweep s of the call has the global index g = first_sweep + s and visits the columns
+ *      c = 0 .. N^2 - 1 in row-major order.  Later columns see earlier updates.
+ *   3. for column c: a_min = min_k a(c, k); w_k = T_s[min(a(c, k) - a_min, D - 1)], T_s = the caller's row for sweep s (uint32,
+ *      D = table_len entries, 1 <= D <= MCQ_MAX_HEATBATH_TABLE); C_k = w_0 + .. + w_k in uint32 (k = 0 .. N - 1), W = C_{N-1}.
+ *      The Python side builds T_s[d] = floor(2^24 exp(-beta_s d)) in float64 with NumPy, beta_s >= 0, so T_s[0] = 2^24 and
+ *      W <= 128 * 2^24 = 2^31; D = 1 + the first d with T = 0 over the call's rows, at most 512, rows zero-padded.
+ *   4. one 32-bit word x per (chain, sweep, column): word w = g N^2 + c (64-bit) of chain r is
+ *      philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[r], 1))[w % 4] -- the definition of
+ *      MCQ_RNG_PHILOX4X32_10 with key word 1 instead of 0, so the two streams are independent.  The state of a chain is its placement
+ *      plus a sweep index, and nothing else.
+ *   5. U = floor(x W / 2^32) from the full 64-bit product; the new height is the smallest k with C_k > U.
+ *      E += a(c, k_new) - a(c, k_old); n_changed counts the updates with k_new != k_old.
+ *   6. best values are taken at sweep ends only: initially best_energy = the recount of the clamped input, best_sweep = 0 and
+ *      best_state = the clamped input; after sweep s a STRICTLY lower E sets best_energy, best_sweep = s + 1 (relative to the call)
+ *      and best_state.  energy_hist[r][0 .. n_sweeps] (optional) holds the recount, then E after each sweep.
+ *   7. so: n_sweeps = 0 is a recount and a copy; state_out may be state_in (chains do not interact); D = 1 makes every update uniform,
+ *      k = floor(x N / 2^32), whatever the placement; a run cut into calls with first_sweep carried over is the unbroken run.
+ * best_sweep and n_changed are int64, so that mcq_resample_device's fold takes them as seg_steps_to_best / seg_n_accepted with
+ * first_step = first_sweep (steps read as sweeps).
+ */
+#define MCQ_MAX_HEATBATH_TABLE 512
+#define MCQ_HEATBATH_WEIGHT_BITS 24
+
+typedef struct mcq_heatbath {
+    int32_t N;             /* MCQ_MIN_N .. MCQ_MAX_N_BOARD */
+    int32_t mode;          /* MCQ_MODE_BOARD; full_3d is MCQ_EINVAL */
+    int64_t n_chains;      /* 1 .. 2^31 - 1 */
+    int64_t n_sweeps;      /* >= 0 */
+    int64_t first_sweep;   /* >= 0: global index of the call's sweep 0; (first_sweep + n_sweeps) N^2 < 2^63 */
+    const uint32_t* seeds; /* [n_chains] */
+    const uint32_t* table; /* [n_sweeps][table_len]: T_s; may be NULL when n_sweeps = 0 */
+    int64_t table_len;     /* D, 1 .. MCQ_MAX_HEATBATH_TABLE */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;    /* [n_chains][N*N]; may be state_in */
+    int32_t* energy_in;    /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;   /* optional [n_chains]: E of the output = energy_in + the sum of the updates' differences */
+    int32_t* best_energy;  /* optional [n_chains] */
+    int64_t* best_sweep;   /* optional [n_chains] */
+    uint8_t* best_state;   /* optional [n_chains][N*N]; neither state_in nor state_out */
+    int64_t* n_changed;    /* optional [n_chains] */
+    int32_t* energy_hist;  /* optional [n_chains][hist_stride] */
+    int64_t hist_stride;   /* int32 entries per chain row of energy_hist, >= n_sweeps + 1 (read only when energy_hist is given) */
+} mcq_heatbath;
+
+/* the message of the last error of the calling thread from the two mcq_heatbath_* calls below (they do not set mcq_last_error()) */
+const char* mcq_heatbath_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`; asynchronous: nothing is copied back and nothing
+ * synchronises.  MCQ_EINVAL before any launch: mode other than board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative
+ * n_sweeps or first_sweep, (first_sweep + n_sweeps) N^2 >= 2^63, table_len outside 1 .. 512, a NULL seeds, state_in or state_out, a NULL
+ * table with n_sweeps > 0, hist_stride < n_sweeps + 1 with energy_hist given.  NOT checked, being on the device: a table with
+ * T[0] = 0 can give W = 0, and the column then takes the height N - 1; nothing leaves the arrays. */
+int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+int mcq_heatbath_host(const mcq_heatbath* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -185,6 +185,11 @@ def lib():
         L.mcq_quench_device.argtypes = [C.POINTER(abi.Quench), C.c_void_p]
         L.mcq_quench_host.restype = C.c_int
         L.mcq_quench_host.argtypes = [C.POINTER(abi.Quench)]
+        L.mcq_heatbath_last_error.restype = C.c_char_p
+        L.mcq_heatbath_device.restype = C.c_int
+        L.mcq_heatbath_device.argtypes = [C.POINTER(abi.Heatbath), C.c_void_p]
+        L.mcq_heatbath_host.restype = C.c_int
+        L.mcq_heatbath_host.argtypes = [C.POINTER(abi.Heatbath)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -224,6 +229,28 @@ def _check_quench(rc):
     if rc == abi.ENOMEM:
         raise MemoryError(msg)
     raise McqError(msg)
+
+
+def _check_heatbath(rc):
+    """_check for the mcq_heatbath_* calls, which keep their own message (mcq_heatbath_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_heatbath_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def heatbath_host(q):
+    """mcq_heatbath_host on a filled abi.Heatbath block of HOST pointers.  Pure host code, no GPU."""
+    _check_heatbath(lib().mcq_heatbath_host(C.byref(q)))
+
+
+def heatbath_device(q, stream):
+    """mcq_heatbath_device on a filled abi.Heatbath block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_heatbath(lib().mcq_heatbath_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def quench_host(q):

@@ -164,6 +164,53 @@ class Quench(C.Structure):
 QUENCH_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.int32, "n_passes": np.int32, "conflicts": np.uint16}
 
 
+MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
+HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
+
+
+class Heatbath(C.Structure):
+    """include/mcq.h: mcq_heatbath -- heat-bath column sweeps of board placements"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_sweeps", C.c_int64),
+        ("first_sweep", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("table", C.c_void_p),
+        ("table_len", C.c_int64),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_sweep", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_changed", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+    ]
+
+
+# the per-chain outputs of a heat-bath call besides the placements: field -> dtype
+HEATBATH_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "best_energy": np.int32, "best_sweep": np.int64, "n_changed": np.int64}
+
+
+def heatbath_table(betas):
+    """The weight rows of a heat-bath call (include/mcq.h, heat-bath rule, step 3): T[s][d] = floor(2^24 exp(-beta_s d)) as uint32 for
+    d = 0 .. D - 1, one row per sweep; D = 1 + the first d with T = 0 over the rows, at most 512, the rows zero-padded.  NumPy's exp /
+    floor on float64.  No sweep gives one row [2^24] that no sweep reads."""
+    b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+    if not (np.isfinite(b).all() and (b >= 0.0).all()):
+        raise ValueError("the heat-bath sweep needs finite beta >= 0 for every sweep")
+    if b.size == 0:
+        return np.full((1, 1), 1 << HEATBATH_WEIGHT_BITS, dtype=np.uint32)
+    d = np.arange(MAX_HEATBATH_TABLE, dtype=np.float64)
+    t = np.floor(float(1 << HEATBATH_WEIGHT_BITS) * np.exp(-b[:, None] * d[None, :])).astype(np.uint32)
+    support = int((t != 0).any(axis=0).sum())  # the rows fall monotonically: the first all-zero d
+    return np.ascontiguousarray(t[:, : min(support + 1, MAX_HEATBATH_TABLE)])
+
+
 class PackSlot(C.Structure):
     """include/mcq.h: mcq_pack_slot -- where one job's fields sit in the packed summary tensor (word offsets, -1 = absent)"""
     _fields_ = [("counters", C.c_int64), ("min_slot", C.c_int64), ("best", C.c_int64), ("stb", C.c_int64), ("stats", C.c_int64)]

@@ -1,0 +1,410 @@
+// mcq_heatbath.hip -- heat-bath column sweeps of board placements (include/mcq.h: mcq_heatbath, where the rule is stated).  Like the quench
+// (csrc/mcq_quench.hip) it sits outside the Metropolis sweep: placements in device memory in, placements and per-chain figures out.
+//
+//   kernel  the lanes of a GROUP are the candidate heights k of one column, as in the quench: 16, 32 or 64 lanes for N <= 16, 32, 64 and
+//           64 lanes with two heights each (k and k + 64) beyond; a wavefront holds 4, 2 or 1 chains, a workgroup is one wavefront.
+//           What differs from the quench is how a column's cells are fetched.  The chain keeps FOUR copies of its heights in LDS, one per
+//           line family: by row, by board column, by diagonal (line i - j + N - 1) and by anti-diagonal (line i + j), each line NP bytes
+//           long (NP = N rounded up to the instantiation's padding), indexed by j for the rows and by i for the other three, and holding
+//           255 where the line has no cell.  The four lines through a column are then 4 NP contiguous bytes: they are fetched as whole
+//           dwords (ds_read2_b32 / ds_read_b32, wider where the alignment is known), all issued before the first test, and the bytes are taken
+//           apart in registers.  255 never counts (|255 - k| >= 128 > d), so the walk has no range checks and no branches; the column's own
+//           cell sits on all four lines at distance 0 and counts once per line for k = h(c): a(c, k) = the count - 4 [k = h(c)].
+//           The minimum runs over the group with DPP row rotations (16 lanes) and __shfl_xor beyond, the prefix sum with DPP row shifts
+//           and the row totals, the selection is a ballot of C_k <= U, and one Philox block serves four columns.  The sweep's table row
+//           is staged in LDS once per sweep.  A changed height is stored to the four copies by EVERY lane of the group (same address,
+//           same value), so each lane's later reads are ordered behind its own store by program order, as in the quench.
+//   host    mcq_heatbath_host: the same rule over host buffers, column by column with a plain table a[k].
+//
+// Built for gfx950 only, with csrc/mcq_hip.hip:  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstdarg>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/mcq.h"
+
+namespace {
+
+thread_local char g_heatbath_err[256] = "";
+
+int heatbath_fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_heatbath_err, sizeof g_heatbath_err, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+// philox4x32-10: counter (c0, c1, 0, 0), key (k0, k1)
+__host__ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+    uint32_t c2 = 0, c3 = 0;
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
+        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+    }
+    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+struct HeatbathArgs {
+    const uint32_t* seeds;
+    const uint32_t* table;
+    const uint8_t* state_in;
+    uint8_t* state_out;
+    int32_t* energy_in;
+    int32_t* energy_out;
+    int32_t* best_energy;
+    int64_t* best_sweep;
+    uint8_t* best_state;
+    int64_t* n_changed;
+    int32_t* energy_hist;
+    long long hist_stride;
+    long long n_chains;
+    long long n_sweeps;
+    long long first_sweep;
+    int table_len;
+    int N;
+};
+
+// DPP within a row of 16 lanes: the value of the lane `n` below (0 where the row ends) / of the lane n to the right, cyclically
+template <int n>
+__device__ __forceinline__ uint32_t row_shr(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x110 + n, 0xF, 0xF, false);
+}
+template <int n>
+__device__ __forceinline__ int row_ror(int v) {
+    return __builtin_amdgcn_update_dpp(v, v, 0x120 + n, 0xF, 0xF, false);
+}
+
+template <int GW>
+__device__ __forceinline__ int group_min(int v) {
+    v = min(v, row_ror<1>(v));
+    v = min(v, row_ror<2>(v));
+    v = min(v, row_ror<4>(v));
+    v = min(v, row_ror<8>(v));
+    for (int o = 16; o < GW; o <<= 1) v = min(v, __shfl_xor(v, o, GW));
+    return v;
+}
+
+// inclusive prefix sum over the lanes of a group; `total` = the group's sum
+template <int GW>
+__device__ __forceinline__ uint32_t group_scan(uint32_t v, int lane, uint32_t& total) {
+    v += row_shr<1>(v);
+    v += row_shr<2>(v);
+    v += row_shr<4>(v);
+    v += row_shr<8>(v);
+    if (GW == 16) {
+        total = __shfl(v, 15, GW);
+        return v;
+    }
+    const uint32_t r0 = __shfl(v, 15, GW), r1 = __shfl(v, 31, GW);
+    uint32_t add = lane >= 16 ? r0 : 0;
+    total = r0 + r1;
+    if (GW == 64) {
+        const uint32_t r2 = __shfl(v, 47, GW), r3 = __shfl(v, 63, GW);
+        add += (lane >= 32 ? r1 : 0) + (lane >= 48 ? r2 : 0);
+        total += r2 + r3;
+    }
+    return v + add;
+}
+
+// the cells of one line (NP bytes, 255 = no cell) against this lane's heights: a cell at index idx of height hp counts when
+// |hp - k| is 0 or |idx - pos|
+template <int KPL, int NP>
+__device__ __forceinline__ void line_hits(const uint32_t* line, int pos, int k0, int k1, int& c0, int& c1) {
+    constexpr int UN = NP <= 32 ? NP / 4 : 4;
+#pragma unroll UN
+    for (int w = 0; w < NP / 4; w++) {
+        const uint32_t v = line[w];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int hp = (int)((v >> (8 * b)) & 255u);
+            const int d = abs(4 * w + b - pos);
+            const int a0 = abs(hp - k0);
+            c0 += (a0 == 0) | (a0 == d);
+            if (KPL == 2) {
+                const int a1 = abs(hp - k1);
+                c1 += (a1 == 0) | (a1 == d);
+            }
+        }
+    }
+}
+
+template <int GW, int KPL, int NP>
+__global__ __launch_bounds__(64) void mcq_heatbath_kernel(HeatbathArgs a) {
+    constexpr int CPW = 64 / GW;       // chains per wavefront
+    constexpr int NPW = NP / 4;        // dwords per line
+    constexpr int FAM = NP * NPW;      // dwords of the row copy (and of the column copy); the two diagonal copies take 2 FAM each
+    constexpr int CHAIN = 6 * FAM;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[CPW * CHAIN];
+    __shared__ uint32_t tab[512];
+    const int N = a.N, Q = N * N, D = a.table_len;
+    const int lane = threadIdx.x & (GW - 1), grp = threadIdx.x / GW;
+    const long long chain = (long long)blockIdx.x * CPW + grp;
+    const bool valid = chain < a.n_chains;
+    const long long ch = valid ? chain : a.n_chains - 1;  // a group beyond the last chain walks the last chain and writes nothing
+    uint32_t* base = lds + grp * CHAIN;
+    uint8_t* rows = (uint8_t*)base;
+    uint8_t* cols = rows + 4 * FAM;
+    uint8_t* diag = rows + 8 * FAM;
+    uint8_t* anti = rows + 16 * FAM;
+    for (int w = lane; w < CHAIN; w += GW) base[w] = 0xFFFFFFFFu;
+    __syncthreads();
+    const uint8_t* in = a.state_in + ch * Q;
+    for (int c = lane; c < Q; c += GW) {
+        const int v = in[c], i = c / N, j = c - i * N;
+        const uint8_t hv = (uint8_t)(v < N ? v : N - 1);
+        rows[i * NP + j] = hv;
+        cols[j * NP + i] = hv;
+        diag[(i - j + N - 1) * NP + i] = hv;
+        anti[(i + j) * NP + i] = hv;
+    }
+    __syncthreads();
+    if (valid && a.best_state) {  // until a sweep end is strictly lower: the (clamped) input
+        uint8_t* out = a.best_state + ch * Q;
+        for (int c = lane; c < Q; c += GW) {
+            const int i = c / N;
+            out[c] = rows[i * NP + (c - i * N)];
+        }
+    }
+    const int k0 = lane, k1 = lane + 64;
+    const uint32_t seed = a.seeds[ch];
+    int32_t* hist = a.energy_hist ? a.energy_hist + ch * a.hist_stride : nullptr;
+
+    int E = 0, e_in = 0, best = 0;
+    long long best_sweep = 0, changed = 0;
+    uint32_t rnd[4] = {0, 0, 0, 0};
+    // sweep -1 is the recount of the input: the same walk with no update
+    for (long long s = -1; s < a.n_sweeps; s++) {
+        const bool recount = s < 0;
+        if (!recount) {
+            __syncthreads();
+            const uint32_t* row = a.table + s * D;
+            for (int d = threadIdx.x; d < D; d += 64) tab[d] = row[d];
+            __syncthreads();
+        }
+        const unsigned long long w0 = recount ? 0ull : (unsigned long long)(a.first_sweep + s) * (unsigned long long)Q;
+        int twoE = 0;
+        for (int i = 0, c = 0; i < N; i++)
+            for (int j = 0; j < N; j++, c++) {
+                int c0 = 0, c1 = 0;
+                const int dl = i - j + N - 1, al = i + j;
+                line_hits<KPL, NP>(base + i * NPW, j, k0, k1, c0, c1);
+                line_hits<KPL, NP>(base + FAM + j * NPW, i, k0, k1, c0, c1);
+                line_hits<KPL, NP>(base + 2 * FAM + dl * NPW, i, k0, k1, c0, c1);
+                line_hits<KPL, NP>(base + 4 * FAM + al * NPW, i, k0, k1, c0, c1);
+                const int cur = rows[i * NP + j];
+                c0 -= k0 == cur ? 4 : 0;
+                if (KPL == 2) c1 -= k1 == cur ? 4 : 0;
+                const int a_old = __shfl(KPL == 2 && cur >= 64 ? c1 : c0, cur & (GW - 1), GW);
+                if (recount) {
+                    twoE += a_old;
+                    continue;
+                }
+                int m = k0 < N ? c0 : INT_MAX;
+                if (KPL == 2) m = min(m, k1 < N ? c1 : INT_MAX);
+                const int a_min = group_min<GW>(m);
+                const uint32_t wt0 = k0 < N ? tab[k0 < N ? min(c0 - a_min, D - 1) : 0] : 0u;
+                uint32_t W, C0 = group_scan<GW>(wt0, lane, W), C1 = 0;
+                if (KPL == 2) {
+                    const uint32_t wt1 = k1 < N ? tab[k1 < N ? min(c1 - a_min, D - 1) : 0] : 0u;
+                    uint32_t W1;
+                    C1 = W + group_scan<GW>(wt1, lane, W1);
+                    W += W1;
+                }
+                const unsigned long long w = w0 + (unsigned)c;
+                if ((w & 3) == 0 || c == 0) philox_block((uint32_t)(w >> 2), (uint32_t)(w >> 34), seed, 1u, rnd);
+                const int e = (int)(w & 3);
+                const uint32_t x = e == 0 ? rnd[0] : e == 1 ? rnd[1] : e == 2 ? rnd[2] : rnd[3];
+                const uint32_t U = __umulhi(x, W);
+                // the smallest k with C_k > U = the number of heights with C_k <= U (C is non-decreasing; a lane beyond N holds W > U)
+                const unsigned long long gmask = GW == 64 ? ~0ull : ((1ull << GW) - 1);
+                int kn = __popcll((__ballot(C0 <= U) >> (grp * GW)) & gmask);
+                if (KPL == 2) kn += __popcll(__ballot(C1 <= U));
+                kn = min(kn, N - 1);  // (only a table with T[0] = 0, W = 0, gets here: the last height, as in the host code)
+                const int a_new = __shfl(KPL == 2 && kn >= 64 ? c1 : c0, kn & (GW - 1), GW);
+                E += a_new - a_old;
+                changed += kn != cur;
+                const uint8_t hv = (uint8_t)kn;
+                rows[i * NP + j] = hv;
+                cols[j * NP + i] = hv;
+                diag[dl * NP + i] = hv;
+                anti[al * NP + i] = hv;
+            }
+        if (recount) {
+            E = e_in = best = twoE >> 1;
+            if (valid && hist && lane == 0) hist[0] = E;
+            continue;
+        }
+        if (valid && hist && lane == 0) hist[s + 1] = E;
+        if (E < best) {
+            best = E;
+            best_sweep = s + 1;
+            if (valid && a.best_state) {
+                uint8_t* out = a.best_state + ch * Q;
+                for (int c = lane; c < Q; c += GW) {
+                    const int i = c / N;
+                    out[c] = rows[i * NP + (c - i * N)];
+                }
+            }
+        }
+    }
+    if (!valid) return;
+    uint8_t* out = a.state_out + ch * Q;
+    for (int c = lane; c < Q; c += GW) {
+        const int i = c / N;
+        out[c] = rows[i * NP + (c - i * N)];
+    }
+    if (lane == 0) {
+        if (a.energy_in) a.energy_in[ch] = e_in;
+        if (a.energy_out) a.energy_out[ch] = E;
+        if (a.best_energy) a.best_energy[ch] = best;
+        if (a.best_sweep) a.best_sweep[ch] = best_sweep;
+        if (a.n_changed) a.n_changed[ch] = changed;
+    }
+}
+
+// what both entry points refuse
+int check_heatbath(const mcq_heatbath* q) {
+    if (!q) return heatbath_fail(MCQ_EINVAL, "mcq_heatbath: NULL parameter block");
+    if (q->mode != MCQ_MODE_BOARD) return heatbath_fail(MCQ_EINVAL, "mode: the heat-bath sweep runs boards only (MCQ_MODE_BOARD), got %d", (int)q->mode);
+    if (q->N < MCQ_MIN_N || q->N > MCQ_MAX_N_BOARD) return heatbath_fail(MCQ_EINVAL, "N out of range [%d, %d]: %d", MCQ_MIN_N, MCQ_MAX_N_BOARD, (int)q->N);
+    if (q->n_chains < 1 || q->n_chains > INT_MAX) return heatbath_fail(MCQ_EINVAL, "n_chains out of range [1, 2^31 - 1]: %lld", (long long)q->n_chains);
+    if (q->n_sweeps < 0) return heatbath_fail(MCQ_EINVAL, "n_sweeps must be >= 0, got %lld", (long long)q->n_sweeps);
+    if (q->first_sweep < 0) return heatbath_fail(MCQ_EINVAL, "first_sweep must be >= 0, got %lld", (long long)q->first_sweep);
+    const uint64_t end = (uint64_t)q->first_sweep + (uint64_t)q->n_sweeps, Q = (uint64_t)q->N * (uint64_t)q->N;
+    if (end > (uint64_t)INT64_MAX / Q)
+        return heatbath_fail(MCQ_EINVAL, "first_sweep + n_sweeps = %llu: the word index (first_sweep + n_sweeps) N^2 must stay below 2^63", (unsigned long long)end);
+    if (q->table_len < 1 || q->table_len > MCQ_MAX_HEATBATH_TABLE)
+        return heatbath_fail(MCQ_EINVAL, "table_len out of range [1, %d]: %lld", MCQ_MAX_HEATBATH_TABLE, (long long)q->table_len);
+    if (!q->seeds) return heatbath_fail(MCQ_EINVAL, "seeds is required");
+    if (!q->table && q->n_sweeps > 0) return heatbath_fail(MCQ_EINVAL, "table is required (n_sweeps rows of table_len words)");
+    if (!q->state_in) return heatbath_fail(MCQ_EINVAL, "state_in is required");
+    if (!q->state_out) return heatbath_fail(MCQ_EINVAL, "state_out is required");
+    if (q->energy_hist && q->hist_stride < q->n_sweeps + 1)
+        return heatbath_fail(MCQ_EINVAL, "hist_stride must be >= n_sweeps + 1 = %lld, got %lld", (long long)q->n_sweeps + 1, (long long)q->hist_stride);
+    return MCQ_OK;
+}
+
+template <int GW, int KPL, int NP>
+void launch_heatbath(const HeatbathArgs& a, hipStream_t s) {
+    constexpr int CPW = 64 / GW;
+    hipLaunchKernelGGL((mcq_heatbath_kernel<GW, KPL, NP>), dim3((unsigned)((a.n_chains + CPW - 1) / CPW)), dim3(64), 0, s, a);
+}
+
+// a[k] = a(c, k) of column (i, j), k = 0 .. N - 1 (the quench's rule, items 1 - 2)
+void host_counts(const uint8_t* h, int N, int i, int j, int* a) {
+    for (int k = 0; k < N; k++) a[k] = 0;
+    auto hit = [&](int hp, int d) {
+        a[hp]++;
+        if (hp - d >= 0) a[hp - d]++;
+        if (hp + d < N) a[hp + d]++;
+    };
+    for (int jj = 0; jj < N; jj++) {  // the row, and the two diagonal cells of board column jj
+        if (jj == j) continue;
+        const int d = jj > j ? jj - j : j - jj;
+        hit(h[i * N + jj], d);
+        if (i + d < N) hit(h[(i + d) * N + jj], d);
+        if (i - d >= 0) hit(h[(i - d) * N + jj], d);
+    }
+    for (int ii = 0; ii < N; ii++)  // the board column
+        if (ii != i) hit(h[ii * N + j], ii > i ? ii - i : i - ii);
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* mcq_heatbath_last_error(void) { return g_heatbath_err; }
+
+int mcq_heatbath_host(const mcq_heatbath* q) {
+    const int rc = check_heatbath(q);
+    if (rc != MCQ_OK) return rc;
+    const int N = q->N, Q = N * N, D = (int)q->table_len;
+    std::vector<uint8_t> h((size_t)Q);
+    std::vector<int> a((size_t)N);
+    std::vector<uint32_t> C((size_t)N);
+    for (long long ch = 0; ch < q->n_chains; ch++) {
+        const uint8_t* in = q->state_in + ch * Q;
+        for (int c = 0; c < Q; c++) h[(size_t)c] = (uint8_t)(in[c] < N ? in[c] : N - 1);
+        long long twoE = 0;
+        for (int c = 0; c < Q; c++) {
+            host_counts(h.data(), N, c / N, c % N, a.data());
+            twoE += a[h[(size_t)c]];
+        }
+        const int e_in = (int)(twoE / 2);
+        int E = e_in, best = e_in;
+        long long best_sweep = 0, changed = 0;
+        int32_t* hist = q->energy_hist ? q->energy_hist + ch * q->hist_stride : nullptr;
+        if (hist) hist[0] = e_in;
+        if (q->best_state)
+            for (int c = 0; c < Q; c++) q->best_state[ch * Q + c] = h[(size_t)c];
+        const uint32_t seed = q->seeds[ch];
+        for (long long s = 0; s < q->n_sweeps; s++) {
+            const uint32_t* T = q->table + s * D;
+            const uint64_t w0 = (uint64_t)(q->first_sweep + s) * (uint64_t)Q;
+            for (int c = 0; c < Q; c++) {
+                host_counts(h.data(), N, c / N, c % N, a.data());
+                int a_min = a[0];
+                for (int k = 1; k < N; k++) a_min = a[k] < a_min ? a[k] : a_min;
+                uint32_t sum = 0;
+                for (int k = 0; k < N; k++) {
+                    const int d = a[k] - a_min;
+                    sum += T[d < D - 1 ? d : D - 1];
+                    C[(size_t)k] = sum;
+                }
+                const uint64_t w = w0 + (uint64_t)c;
+                uint32_t r[4];
+                philox_block((uint32_t)(w >> 2), (uint32_t)(w >> 34), seed, 1u, r);
+                const uint32_t U = (uint32_t)(((uint64_t)r[w & 3] * (uint64_t)sum) >> 32);
+                int kn = 0;
+                while (kn < N - 1 && C[(size_t)kn] <= U) kn++;  // (a table with T[0] = 0 gives W = 0: the last height, nothing leaves the arrays)
+                const int cur = h[(size_t)c];
+                E += a[kn] - a[cur];
+                changed += kn != cur;
+                h[(size_t)c] = (uint8_t)kn;
+            }
+            if (hist) hist[s + 1] = E;
+            if (E < best) {
+                best = E;
+                best_sweep = s + 1;
+                if (q->best_state)
+                    for (int c = 0; c < Q; c++) q->best_state[ch * Q + c] = h[(size_t)c];
+            }
+        }
+        uint8_t* out = q->state_out + ch * Q;
+        for (int c = 0; c < Q; c++) out[c] = h[(size_t)c];
+        if (q->energy_in) q->energy_in[ch] = e_in;
+        if (q->energy_out) q->energy_out[ch] = E;
+        if (q->best_energy) q->best_energy[ch] = best;
+        if (q->best_sweep) q->best_sweep[ch] = best_sweep;
+        if (q->n_changed) q->n_changed[ch] = changed;
+    }
+    return MCQ_OK;
+}
+
+int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream) {
+    const int rc = check_heatbath(q);
+    if (rc != MCQ_OK) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const HeatbathArgs a{q->seeds, q->table, q->state_in, q->state_out, q->energy_in, q->energy_out, q->best_energy, q->best_sweep, q->best_state,
+                         q->n_changed, q->energy_hist, (long long)q->hist_stride, (long long)q->n_chains, (long long)q->n_sweeps,
+                         (long long)q->first_sweep, (int)q->table_len, (int)q->N};
+    const int N = q->N;
+    if (N <= 8) launch_heatbath<16, 1, 8>(a, s);
+    else if (N <= 12) launch_heatbath<16, 1, 12>(a, s);
+    else if (N <= 16) launch_heatbath<16, 1, 16>(a, s);
+    else if (N <= 24) launch_heatbath<32, 1, 24>(a, s);
+    else if (N <= 32) launch_heatbath<32, 1, 32>(a, s);
+    else if (N <= 64) launch_heatbath<64, 1, 64>(a, s);
+    else launch_heatbath<64, 2, 128>(a, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return heatbath_fail(MCQ_EDEVICE, "mcq_heatbath_device: %s", hipGetErrorString(e));
+    return MCQ_OK;
+}
+
+}  // extern "C"
