@@ -541,6 +541,61 @@ int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
 int mcq_heatbath_host(const mcq_heatbath* q);
 
+/*
+ * Quench of full_3d placements: the deterministic zero-temperature descent of Q queens in the N^3 cube to a local minimum under
+ * single-queen moves (csrc/mcq_quench3d.hip) -- NOT a mode of the reference, which ships the ingredient
+ * (State3DQueens.conflicts_for_queen, mcmc.py:185-226) and never calls it; never a default, like Philox, replica exchange, population
+ * annealing, the board quench and the heat-bath sweep.  It recounts a placement's energy on the device independently of the sweep,
+ * says whether the placement is a local minimum and which minimum lies below it, and hands back the per-queen conflict map.
+ * mcq_quench above keeps refusing full_3d: a queen here has N^3 targets, and this is the different design.  The rule is integer-exact:
+ *   1. a placement is Q triples (i, j, k) of bytes, the final_state / best_state layout of a full_3d run (3 Q bytes,
+ *      mcq_state_bytes_for).  Every byte is clamped to N - 1 first.  If two queens then hold the same cell the placement is REPEATED:
+ *      bit 0 of flags (MCQ_QUENCH3D_REPEATED) is set, energy_in is still the recount (a shared cell counts as an attacking pair, as
+ *      _compute_energy counts it), state_out is the clamped input, energy_out = energy_in, n_moves = n_passes = 0, and conflicts holds
+ *      a(q, pos(q)) of that placement.  The sweep never produces such a placement.
+ *   2. two distinct cells attack each other iff the non-zero ones among |di|, |dj|, |dk| are all equal: the 13 line directions, the
+ *      reference's seven predicates.  a(q, t) = the number of queens q' != q whose cell is t or attacks t
+ *      (= conflicts_for_queen(q, t) for every cell t, occupied ones included); E = 1/2 sum_q a(q, pos(q)) (= _compute_energy);
+ *      a <= min(Q - 1, 13 (N - 1)) <= 403.
+ *   3. one PASS visits the queens in index order q = 0 .. Q - 1.  The candidates of q are the cells that hold no OTHER queen (its
+ *      own cell is one of them); t* is the candidate with the smallest a(q, t), ties to the smallest cell index i N^2 + j N + k.
+ *      q moves to t* iff a(q, t*) < a(q, pos(q)); E moves by the difference, one move is counted, and later queens of the pass see
+ *      the move.
+ *   4. passes repeat until one moves nothing (the placement is then a local minimum) or max_passes passes have run (0 = no limit).
+ *      Every moving pass lowers E by at least 1, so a run ends within energy_in + 1 passes; n_passes counts the last, moveless pass
+ *      too: a local minimum comes back with n_moves = 0, n_passes = 1.
+ *   5. N = 2 .. MCQ_MAX_N_QUENCH3D (32: a cell index then fits 15 bits, as in the sweep's packed queen table) and
+ *      2 <= Q <= N^3 - 1 (n_queens = 0 means N^2).  Everything else, N = 33 .. 64 included, is refused before any launch.
+ * Chains do not interact, so state_out may be state_in.
+ */
+#define MCQ_MAX_N_QUENCH3D 32
+#define MCQ_QUENCH3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) input hold the same cell; nothing was moved */
+
+typedef struct mcq_quench3d {
+    int32_t N;            /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t n_queens;     /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;     /* 1 .. 2^31 - 1 */
+    int64_t max_passes;   /* >= 0; 0 = until a pass moves nothing */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;   /* [n_chains][Q][3]; may be state_in */
+    int32_t* energy_in;   /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;  /* optional [n_chains]: E of the output = energy_in + the sum of the moves' differences */
+    int32_t* n_moves;     /* optional [n_chains] */
+    int32_t* n_passes;    /* optional [n_chains] */
+    uint16_t* conflicts;  /* optional [n_chains][Q]: a(q, pos(q)) of the OUTPUT placement; its sum is 2 energy_out */
+    int32_t* flags;       /* optional [n_chains]: MCQ_QUENCH3D_* */
+} mcq_quench3d;
+
+/* the message of the last error of the calling thread from the two mcq_quench3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_quench3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`; asynchronous: nothing is copied back and nothing
+ * synchronises.  MCQ_EINVAL before any launch: a NULL block, N outside 2 .. 32 (33 .. 64 named as this build's limit), n_queens
+ * outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, a negative max_passes, a NULL state_in or state_out. */
+int mcq_quench3d_device(const mcq_quench3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output;
+ * exported for the tests the way mcq_quench_host is. */
+int mcq_quench3d_host(const mcq_quench3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

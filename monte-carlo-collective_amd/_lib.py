@@ -190,6 +190,11 @@ def lib():
         L.mcq_heatbath_device.argtypes = [C.POINTER(abi.Heatbath), C.c_void_p]
         L.mcq_heatbath_host.restype = C.c_int
         L.mcq_heatbath_host.argtypes = [C.POINTER(abi.Heatbath)]
+        L.mcq_quench3d_last_error.restype = C.c_char_p
+        L.mcq_quench3d_device.restype = C.c_int
+        L.mcq_quench3d_device.argtypes = [C.POINTER(abi.Quench3D), C.c_void_p]
+        L.mcq_quench3d_host.restype = C.c_int
+        L.mcq_quench3d_host.argtypes = [C.POINTER(abi.Quench3D)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -261,6 +266,28 @@ def quench_host(q):
 def quench_device(q, stream):
     """mcq_quench_device on a filled abi.Quench block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_quench(lib().mcq_quench_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_quench3d(rc):
+    """_check for the mcq_quench3d_* calls, which keep their own message (mcq_quench3d_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_quench3d_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def quench3d_host(q):
+    """mcq_quench3d_host on a filled abi.Quench3D block of HOST pointers.  Pure host code, no GPU."""
+    _check_quench3d(lib().mcq_quench3d_host(C.byref(q)))
+
+
+def quench3d_device(q, stream):
+    """mcq_quench3d_device on a filled abi.Quench3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_quench3d(lib().mcq_quench3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def resample_plan_host(energies, population, table, offsets):

@@ -164,6 +164,33 @@ class Quench(C.Structure):
 QUENCH_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.int32, "n_passes": np.int32, "conflicts": np.uint16}
 
 
+MAX_N_QUENCH3D = 32            # include/mcq.h: MCQ_MAX_N_QUENCH3D
+QUENCH3D_REPEATED = 1          # MCQ_QUENCH3D_REPEATED: bit 0 of flags
+
+
+class Quench3D(C.Structure):
+    """include/mcq.h: mcq_quench3d -- the zero-temperature descent of full_3d placements to a local minimum"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("max_passes", C.c_int64),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_passes", C.c_void_p),
+        ("conflicts", C.c_void_p),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d quench besides the placements: field -> dtype ("conflicts" has a row of Q per chain)
+QUENCH3D_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.int32, "n_passes": np.int32, "conflicts": np.uint16,
+                   "flags": np.int32}
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 

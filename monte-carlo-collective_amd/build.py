@@ -6,9 +6,10 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(CSRC, "libmcq_hip.so")
-# the sweep and its C-ABI; the restore / checkpoint kernels; population annealing's resampling kernels; the quench; the heat-bath sweep
+# the sweep and its C-ABI; the restore / checkpoint kernels; population annealing's resampling kernels; the quench; the heat-bath sweep;
+# the quench of full_3d placements
 SOURCES = [os.path.join(CSRC, "mcq_hip.hip"), os.path.join(CSRC, "mcq_resume.hip"), os.path.join(CSRC, "mcq_population.hip"),
-           os.path.join(CSRC, "mcq_quench.hip"), os.path.join(CSRC, "mcq_heatbath.hip")]
+           os.path.join(CSRC, "mcq_quench.hip"), os.path.join(CSRC, "mcq_heatbath.hip"), os.path.join(CSRC, "mcq_quench3d.hip")]
 HEADERS = [os.path.join(os.path.dirname(HERE), "include", "mcq.h"), os.path.join(CSRC, "mcq_record.h")]
 HEADER = HEADERS[0]
 # -ffp-contract=off: the reference's schedule / acceptance expressions are evaluated without

@@ -5,7 +5,11 @@ NOT a mode of the reference -- it ships conflicts_for_position (mcmc_board.py:14
 labelled as such like Philox, replica exchange and population annealing.  What a sweep hands back (best_state, final_state, the
 competition board) is whatever a thermal chain last held; the quench says whether that placement is a local minimum under
 single-height moves, what the minimum below it is, recounts its energy on the device independently of the sweep, and returns the
-per-column conflict map.  Boards only, N = 2 .. 128.
+per-column conflict map.  Boards: N = 2 .. 128 (quench_states*, quench_device).
+
+full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_quench3d; csrc/mcq_quench3d.hip), N = 2 .. 32 and
+2 <= Q <= N^3 - 1: quench_queens, quench_queens_device, quench_queens_host.  The same labels apply -- the reference ships
+conflicts_for_queen (mcmc.py:185-226) and never calls it.
 """
 import numpy as np
 
@@ -109,3 +113,104 @@ def to_numpy(res):
     if "conflicts" in out:
         out["conflicts"] = out["conflicts"].view(np.uint16)
     return out
+
+
+FIELDS_3D = ("state", "energy_in", "energy_out", "n_moves", "n_passes", "conflicts", "flags")
+
+
+def _block3d(N, Q, n, max_passes):
+    q = abi.Quench3D()
+    q.N, q.n_queens, q.n_chains, q.max_passes = int(N), int(Q), int(n), int(max_passes)
+    return q
+
+
+def _queens_of(N, Q):
+    return int(N) * int(N) if Q is None or int(Q) == 0 else int(Q)
+
+
+def _host_queens(N, states, Q):
+    """uint8[n][3 Q] from uint8[n][3 Q] or [n][Q][3] (one placement [Q][3] or [3 Q] is taken as one chain)."""
+    s = np.ascontiguousarray(states, dtype=np.uint8)
+    Q = _queens_of(N, Q)
+    if s.size == 0:
+        return s.reshape(0, 3 * max(Q, 0))
+    if s.ndim == 1 or (s.ndim == 2 and s.shape == (Q, 3)):  # one placement
+        s = s.reshape(1, -1)
+    s = s.reshape(s.shape[0], -1)
+    if abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and Q >= 2 and s.shape[1] != 3 * Q:
+        raise ValueError(f"states must be uint8[n_chains][{3 * Q}] or [n_chains][{Q}][3] (final_state layout of full_3d), got {s.shape}")
+    return s
+
+
+def quench_queens_host(N, states, Q=None, max_passes=0, conflicts=True):
+    """mcq_quench3d_host: the full_3d rule in the library's plain host code, NumPy in and out, no GPU.  Same result as quench_queens."""
+    s = _host_queens(N, states, Q)
+    n, Qn = s.shape[0], _queens_of(N, Q)
+    out = {"state": np.zeros_like(s)}
+    for k, dt in abi.QUENCH3D_DTYPES.items():
+        if k != "conflicts" or conflicts:
+            out[k] = np.zeros((n, s.shape[1] // 3) if k == "conflicts" else n, dtype=dt)
+    q = _block3d(N, Qn, n, max_passes)
+    q.state_in, q.state_out = s.ctypes.data, out["state"].ctypes.data
+    for k in abi.QUENCH3D_DTYPES:
+        if k in out:
+            setattr(q, k, out[k].ctypes.data)
+    _lib.quench3d_host(q)
+    return out
+
+
+def quench_queens_device(N, states, Q=None, max_passes=0, out=None, conflicts=True, stream=None):
+    """mcq_quench3d_device on a torch uint8 tensor [n_chains][3 Q] or [n_chains][Q][3] of the current device (e.g.
+    DeviceRun.t["best_state"] of a full_3d run), enqueued on `stream` (default: torch's current stream).  Asynchronous: nothing is copied
+    back and nothing synchronises, so the results are valid once the stream has passed the call.  `out` (optional) is the tensor the
+    placements go to; it may be `states` itself (in place), default a new one.  Returns a dict of tensors: `state` uint8 like `states`,
+    `energy_in` (the recount of the input), `energy_out`, `n_moves`, `n_passes`, `flags` int32[n_chains] and, unless conflicts=False,
+    `conflicts` int16[n_chains][Q] (the uint16 counts a(q, pos(q)) of the output; below 2^15, so the sign bit is never set)."""
+    import torch
+
+    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
+        raise ValueError("quench_queens_device takes a contiguous uint8 tensor on the GPU")
+    Qn = _queens_of(N, Q)
+    ok = (states.dim() == 2 and int(states.shape[1]) == 3 * Qn) or (states.dim() == 3 and tuple(states.shape[1:]) == (Qn, 3))
+    if states.dim() not in (2, 3) or (abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and Qn >= 2 and not ok):
+        raise ValueError(f"states must be uint8[n_chains][{3 * Qn}] or [n_chains][{Qn}][3] (final_state layout of full_3d), got {tuple(states.shape)}")
+    n = int(states.shape[0])
+    dev = states.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        if out is None:
+            out = torch.empty_like(states)
+        elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
+        res = {"state": out}
+        for k in ("energy_in", "energy_out", "n_moves", "n_passes", "flags"):
+            res[k] = torch.empty(n, dtype=torch.int32, device=dev)
+        if conflicts:
+            res["conflicts"] = torch.empty((n, Qn), dtype=torch.int16, device=dev)
+        q = _block3d(N, Qn, n, max_passes)
+        q.state_in, q.state_out = states.data_ptr(), out.data_ptr()
+        for k in abi.QUENCH3D_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.quench3d_device(q, st)
+    return res
+
+
+def quench_queens(N, states, Q=None, max_passes=0, conflicts=True):
+    """Quench full_3d placements on the GPU: `states` is uint8[n_chains][3 Q] or [n_chains][Q][3] (the final_state / best_state layout
+    of a full_3d run: Q triples (i, j, k); Q=None means N^2), bytes >= N are clamped to N - 1.  max_passes = 0 runs until a pass moves
+    nothing.  Returns a dict of NumPy arrays: `state` uint8[n_chains][3 Q] (the placements after the descent), `energy_in` (the energy
+    of the input, recounted on the device), `energy_out`, `n_moves`, `n_passes`, `flags` int32[n_chains], and `conflicts`
+    uint16[n_chains][Q], the number of queens attacking each queen in the output (its sum is 2 energy_out).  A placement with
+    n_moves == 0 and n_passes == 1 was a local minimum already; flags bit 0 (abi.QUENCH3D_REPEATED) marks an input with two queens in
+    one cell, which is recounted and handed back unmoved.  ValueError for what the library refuses (N outside 2 .. 32, Q outside
+    2 .. N^3 - 1, no chain, a negative max_passes)."""
+    import torch
+
+    s = _host_queens(N, states, Q)
+    if s.shape[0] == 0:
+        _lib.quench3d_host(_block3d(N, _queens_of(N, Q), 0, max_passes))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = quench_queens_device(N, torch.from_numpy(s).to(dev), Q=Q, max_passes=max_passes, conflicts=conflicts)
+    torch.cuda.current_stream(dev).synchronize()
+    return to_numpy(res)

@@ -302,6 +302,66 @@ def gen_conflicts(ref_path, out):
     return cases
 
 
+def gen_conflicts3d(ref_path, out):
+    """State3DQueens.conflicts_for_queen (mcmc.py:185-226) and _compute_energy of ~28 full_3d placements: what the quench of full_3d
+    placements (include/mcq.h: mcq_quench3d) is pinned by.  Random, latin and klarner inits, Q != N^2, and end states of the golden
+    full_3d chains.  conflicts_for_queen(q, t) is recorded for every queen q and every cell t up to N = 8, and for every queen and a
+    fixed random sample of cells plus every occupied cell beyond.  conflicts_3d.npz holds data only -- per placement p: p_queens
+    uint8[Q][3], p_cells int32[T] (the cell indices i N^2 + j N + k of the columns of the table; all N^3 up to N = 8), p_table
+    uint16[Q][T], p_energy -- and its own list of cases (`cases`, JSON): the manifest is left alone.
+    `python tools/gen_golden.py --only conflicts3d`."""
+    import contextlib
+    import io
+
+    _ref(ref_path)
+    from mcmc import State3DQueens
+
+    placements = []
+    for N, Q in ((2, None), (3, None), (4, None), (5, None), (6, None), (8, None), (12, None), (16, None), (20, 150), (24, 200), (32, 120)):
+        np.random.seed(700 + N)
+        placements.append((f"random N={N}" + (f" Q={Q}" if Q else ""), N, State3DQueens(N, Q=Q, init_mode="random").queens))
+    for N, Q in ((2, 2), (2, 7), (3, 26), (4, 10), (6, 50), (12, 100)):  # Q != N^2: two queens, one free cell, in between
+        np.random.seed(750 + 7 * N + Q)
+        placements.append((f"random N={N} Q={Q}", N, State3DQueens(N, Q=Q, init_mode="random").queens))
+    for N in (4, 8, 12):
+        placements.append((f"latin N={N}", N, State3DQueens(N, init_mode="latin").queens))
+    for N in (7, 11, 12):  # 12: gcd(12, 210) != 1, the core of M = 11 and random queens around it
+        np.random.seed(780 + N)
+        with contextlib.redirect_stdout(io.StringIO()):
+            placements.append((f"klarner N={N}", N, State3DQueens(N, init_mode="klarner").queens))
+    with open(os.path.join(out, "manifest.json")) as f:
+        manifest = json.load(f)
+    picked = {"chains": {(3, None): 1, (6, None): 2, (12, None): 2}, "chains_q": {(6, 100): 1, (12, 60): 1, (17, 100): 1}}
+    for name, want in picked.items():
+        z = np.load(os.path.join(out, name + ".npz"))
+        left = dict(want)
+        for c in manifest[name]:
+            if c["mode"] != "board" and left.get((c["N"], c.get("Q")), 0) > 0 and c["n_steps"] >= 150:
+                left[(c["N"], c.get("Q"))] -= 1
+                placements.append((f"final state of {name} {c['key']}", c["N"], z[f"{c['key']}_final_state"].reshape(-1, 3)))
+    arrays, cases = {}, []
+    rs = np.random.RandomState(4242)
+    for b, (what, N, queens) in enumerate(placements):
+        st = State3DQueens(N, positions=np.asarray(queens, dtype=int))
+        Q = st.Q
+        if N <= 8:
+            cells = np.arange(N ** 3)
+        else:
+            occupied = (st.queens[:, 0] * N + st.queens[:, 1]) * N + st.queens[:, 2]
+            cells = np.unique(np.concatenate([occupied, rs.choice(N ** 3, size=96, replace=False)]))
+        pos = [(int(c) // (N * N), (int(c) // N) % N, int(c) % N) for c in cells]
+        tab = np.array([[st.conflicts_for_queen(q, t) for t in pos] for q in range(Q)])
+        key = f"p{b:02d}"
+        arrays[key + "_queens"] = np.asarray(st.queens, dtype=np.uint8)
+        arrays[key + "_cells"] = cells.astype(np.int32)
+        arrays[key + "_table"] = tab.astype(np.uint16)
+        arrays[key + "_energy"] = np.int64(st.energy(recompute=True))
+        cases.append({"key": key, "what": what, "N": N, "Q": Q, "all_cells": N <= 8})
+    arrays["cases"] = np.array(json.dumps(cases))
+    np.savez_compressed(os.path.join(out, "conflicts_3d.npz"), **arrays)
+    return cases
+
+
 def gen_beta(ref_path, out):
     """F5: float64 beta(step) tables of the five schedule closures."""
     ex = _ref(ref_path)
@@ -398,9 +458,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", default="/root/reference")
     ap.add_argument("--workers", type=int, default=8)
-    ap.add_argument("--only", default="", help="'q': only the Q != N^2 chains (chains_q.npz); 'big': only the boards beyond N = 32 (chains_big.npz); 'wide': only the full_3d chains beyond N = 32 (chains_wide.npz); 'stream': only the seed=None chains (chains_stream.npz); merged into the existing manifest.  'conflicts': only conflicts.npz, the conflict tables the quench is pinned by (the manifest is left alone)")
+    ap.add_argument("--only", default="", help="'q': only the Q != N^2 chains (chains_q.npz); 'big': only the boards beyond N = 32 (chains_big.npz); 'wide': only the full_3d chains beyond N = 32 (chains_wide.npz); 'stream': only the seed=None chains (chains_stream.npz); merged into the existing manifest.  'conflicts': only conflicts.npz, the conflict tables the quench is pinned by (the manifest is left alone); 'conflicts3d': only conflicts_3d.npz, the same for the quench of full_3d placements")
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
+    if args.only == "conflicts3d":
+        cases = gen_conflicts3d(args.reference, OUT)
+        print(f"wrote {len(cases)} placements to conflicts_3d.npz ({os.path.getsize(os.path.join(OUT, 'conflicts_3d.npz'))} bytes)")
+        return
     if args.only == "conflicts":
         cases = gen_conflicts(args.reference, OUT)
         print(f"wrote {len(cases)} boards to conflicts.npz ({os.path.getsize(os.path.join(OUT, 'conflicts.npz'))} bytes)")
