@@ -596,6 +596,77 @@ int mcq_quench3d_device(const mcq_quench3d* q, void* hip_stream);
  * exported for the tests the way mcq_quench_host is. */
 int mcq_quench3d_host(const mcq_quench3d* q);
 
+/*
+ * Heat-bath queen sweeps of full_3d placements (csrc/mcq_heatbath3d.hip) -- NOT a mode of the reference, whose only move is one random
+ * queen, one random cell and one Metropolis test; never a default, like Philox, replica exchange, population annealing, the two quenches
+ * and the board heat-bath.  With queen q taken out, the attack field of mcq_quench3d holds a(q, t) of every cell at once, so a queen's
+ * new cell is DRAWN from the Boltzmann weights of all its N^3 - Q + 1 targets and no proposal is rejected.  mcq_heatbath above keeps
+ * refusing full_3d.  The rule is integer-exact:
+ *   1. a placement is Q byte triples (i, j, k) in the final_state layout of full_3d (3 Q bytes); every byte is clamped to N - 1 first.
+ *      N = 2 .. MCQ_MAX_N_QUENCH3D, 2 <= Q <= N^3 - 1 (n_queens = 0 means N^2).  The attack, a(q, t) and E are those of the
+ *      mcq_quench3d rule above, items 1 - 2.  A REPEATED placement (two queens in one cell after clamping) sets bit 0 of flags
+ *      (MCQ_HEATBATH3D_REPEATED) and no sweep is run on it: state_out = best_state = the clamped input, energy_in = energy_out =
+ *      best_energy = the recount (a shared cell counts as a pair), best_sweep = n_changed = 0, and every entry of energy_hist holds the
+ *      recount.
+ *   2. a call runs n_sweeps sweeps; sweep s of the call has the global index g = first_sweep + s and visits the queens q = 0 .. Q - 1 in
+ *      index order.  Later queens see earlier moves.  No queen is skipped: one with a = 0 is updated like any other.
+ *   3. for queen q at cell p: the candidates are the cells that hold no OTHER queen (its own cell is one of them), taken in the order
+ *      of the cell index t = i N^2 + j N + k.  a_min = the smallest a(q, t) over the candidates; w_t = T_s[min(a(q, t) - a_min, D - 1)]
+ *      for a candidate and 0 for an occupied cell, T_s = the caller's row for sweep s (uint32, D = table_len entries,
+ *      1 <= D <= MCQ_MAX_HEATBATH_TABLE; the rows of the board heat-bath, T[d] = floor(2^24 exp(-beta_s d)); a <= 403 < 512).
+ *      C_t = w_0 + .. + w_t over ALL cells in index order, in uint64; W = C_{N^3 - 1} <= 2^15 2^24 = 2^39.
+ *   4. two 32-bit words per (chain, sweep, queen): with u = g Q + q (64-bit) they are the words 2 u and 2 u + 1 of the stream
+ *      word w = philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[r], 2))[w % 4] -- key word 0 is
+ *      MCQ_RNG_PHILOX4X32_10 of the sweep and 1 the board heat-bath, so the three streams are independent.  Both words lie in block
+ *      u / 2, so one block serves two queens.  x = word 2 u | word (2 u + 1) << 32.
+ *   5. U = floor(x W / 2^64), the high half of the 64 x 64 product; the new cell is the smallest t with C_t > U.  W = 0 (only a table
+ *      with T[0] = 0 gives it, which cannot be checked on the device) leaves the queen where it is.  E += a(q, t_new) - a(q, p);
+ *      n_changed counts the updates with t_new != p.
+ *   6. best values are taken at sweep ends only: initially best_energy = the recount of the clamped input, best_sweep = 0 and
+ *      best_state = the clamped input; after sweep s a STRICTLY lower E sets best_energy, best_sweep = s + 1 (relative to the call)
+ *      and best_state.  energy_hist[r][0 .. n_sweeps] (optional) holds the recount, then E after each sweep.  n_sweeps = 0 is a
+ *      recount and a copy.  The state of a chain is its placement plus a sweep index, and nothing else: a run cut into calls with
+ *      first_sweep carried over is the unbroken run.  state_out may be state_in (chains do not interact).
+ *   7. D = 1 makes every update uniform over the candidates, whatever the placement: the new cell is the floor(x F / 2^64)-th
+ *      candidate in index order, F = N^3 - Q + 1.
+ * best_sweep and n_changed are int64, so that mcq_resample_device's fold takes them as seg_steps_to_best / seg_n_accepted with
+ * first_step = first_sweep (steps read as sweeps), as with mcq_heatbath.
+ */
+#define MCQ_HEATBATH3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) input hold the same cell; no sweep was run */
+
+typedef struct mcq_heatbath3d {
+    int32_t N;             /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t n_queens;      /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;      /* 1 .. 2^31 - 1 */
+    int64_t n_sweeps;      /* >= 0 */
+    int64_t first_sweep;   /* >= 0: global index of the call's sweep 0; (first_sweep + n_sweeps) Q < 2^62 */
+    const uint32_t* seeds; /* [n_chains] */
+    const uint32_t* table; /* [n_sweeps][table_len]: T_s; may be NULL when n_sweeps = 0 */
+    int64_t table_len;     /* D, 1 .. MCQ_MAX_HEATBATH_TABLE */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;    /* [n_chains][Q][3]; may be state_in */
+    int32_t* energy_in;    /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;   /* optional [n_chains]: E of the output = energy_in + the sum of the updates' differences */
+    int32_t* best_energy;  /* optional [n_chains] */
+    int64_t* best_sweep;   /* optional [n_chains] */
+    uint8_t* best_state;   /* optional [n_chains][Q][3]; neither state_in nor state_out */
+    int64_t* n_changed;    /* optional [n_chains] */
+    int32_t* energy_hist;  /* optional [n_chains][hist_stride] */
+    int64_t hist_stride;   /* int32 entries per chain row of energy_hist, >= n_sweeps + 1 (read only when energy_hist is given) */
+    int32_t* flags;        /* optional [n_chains]: MCQ_HEATBATH3D_* */
+} mcq_heatbath3d;
+
+/* the message of the last error of the calling thread from the two mcq_heatbath3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_heatbath3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`; asynchronous: nothing is copied back and nothing
+ * synchronises.  MCQ_EINVAL before any launch: a NULL block, seeds, state_in or state_out, a NULL table with n_sweeps > 0, N outside
+ * 2 .. 32 (33 .. 64 named as this build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, a negative
+ * n_sweeps or first_sweep, (first_sweep + n_sweeps) Q >= 2^62, table_len outside 1 .. 512, hist_stride < n_sweeps + 1 with
+ * energy_hist given. */
+int mcq_heatbath3d_device(const mcq_heatbath3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+int mcq_heatbath3d_host(const mcq_heatbath3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

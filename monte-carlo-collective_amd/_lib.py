@@ -195,6 +195,11 @@ def lib():
         L.mcq_quench3d_device.argtypes = [C.POINTER(abi.Quench3D), C.c_void_p]
         L.mcq_quench3d_host.restype = C.c_int
         L.mcq_quench3d_host.argtypes = [C.POINTER(abi.Quench3D)]
+        L.mcq_heatbath3d_last_error.restype = C.c_char_p
+        L.mcq_heatbath3d_device.restype = C.c_int
+        L.mcq_heatbath3d_device.argtypes = [C.POINTER(abi.Heatbath3D), C.c_void_p]
+        L.mcq_heatbath3d_host.restype = C.c_int
+        L.mcq_heatbath3d_host.argtypes = [C.POINTER(abi.Heatbath3D)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -288,6 +293,28 @@ def quench3d_host(q):
 def quench3d_device(q, stream):
     """mcq_quench3d_device on a filled abi.Quench3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_quench3d(lib().mcq_quench3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_heatbath3d(rc):
+    """_check for the mcq_heatbath3d_* calls, which keep their own message (mcq_heatbath3d_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_heatbath3d_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def heatbath3d_host(q):
+    """mcq_heatbath3d_host on a filled abi.Heatbath3D block of HOST pointers.  Pure host code, no GPU."""
+    _check_heatbath3d(lib().mcq_heatbath3d_host(C.byref(q)))
+
+
+def heatbath3d_device(q, stream):
+    """mcq_heatbath3d_device on a filled abi.Heatbath3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_heatbath3d(lib().mcq_heatbath3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def resample_plan_host(energies, population, table, offsets):

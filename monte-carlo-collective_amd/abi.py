@@ -238,6 +238,38 @@ def heatbath_table(betas):
     return np.ascontiguousarray(t[:, : min(support + 1, MAX_HEATBATH_TABLE)])
 
 
+HEATBATH3D_REPEATED = 1        # include/mcq.h: MCQ_HEATBATH3D_REPEATED: bit 0 of flags
+
+
+class Heatbath3D(C.Structure):
+    """include/mcq.h: mcq_heatbath3d -- heat-bath queen sweeps of full_3d placements"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_sweeps", C.c_int64),
+        ("first_sweep", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("table", C.c_void_p),
+        ("table_len", C.c_int64),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_sweep", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_changed", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d heat-bath call besides the placements: field -> dtype
+HEATBATH3D_DTYPES = dict(HEATBATH_DTYPES, flags=np.int32)
+
+
 class PackSlot(C.Structure):
     """include/mcq.h: mcq_pack_slot -- where one job's fields sit in the packed summary tensor (word offsets, -1 = absent)"""
     _fields_ = [("counters", C.c_int64), ("min_slot", C.c_int64), ("best", C.c_int64), ("stb", C.c_int64), ("stats", C.c_int64)]

@@ -3,14 +3,21 @@
 NOT a mode of the reference -- its only move is one random column, one random height and one Metropolis test --, never a default, and
 labelled as such like Philox, replica exchange, population annealing and the quench.  A sweep visits every column in row-major order
 and draws its new height from the Boltzmann weights of all N heights at once, so nothing is rejected.  The rule is integer-exact, so
-the library's host code, the kernel and a NumPy restatement (tests/heatbath_util.py) agree bit for bit.  Boards only, N = 2 .. 128.
+the library's host code, the kernel and a NumPy restatement (tests/heatbath_util.py) agree bit for bit.  Boards: N = 2 .. 128
+(heatbath_states*, heatbath_device).
+
+full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_heatbath3d; csrc/mcq_heatbath3d.hip), N = 2 .. 32 and
+2 <= Q <= N^3 - 1: heatbath_queens, heatbath_queens_device, heatbath_queens_host.  A sweep visits every queen in index order and draws
+its new cell from the Boltzmann weights of all N^3 - Q + 1 cells that hold no other queen.  The same labels apply: NOT a mode of the
+reference, never a default.  anneal_heatbath runs either under a schedule (mcmc_type="board" or "full_3d").
 """
 import numpy as np
 
 from . import _lib, abi
-from .quench import _host_states
+from .quench import _host_queens, _host_states, _queens_of
 
 FIELDS = ("state", "energy_in", "energy_out", "best_energy", "best_sweep", "best_state", "n_changed")
+FIELDS_3D = FIELDS + ("flags",)
 
 
 def _block(N, n, n_sweeps, first_sweep, table):
@@ -66,6 +73,49 @@ def device_table(betas, device):
     return _upload(abi.heatbath_table(betas).view(np.int32), device)
 
 
+def _device_buffers(states, seeds, betas, out, dtypes, trace, best_state):
+    """What heatbath_device and heatbath_queens_device share, on torch's current stream and device: the table and the seeds on the device
+    (checked when given as tensors, uploaded otherwise) and the dict of result tensors.  Returns (table, n_sweeps, seeds, results)."""
+    import torch
+
+    dev, n = states.device, int(states.shape[0])
+    if isinstance(betas, torch.Tensor):  # the rows of device_table, already on the device
+        tab = betas
+        if tab.dtype != torch.int32 or tab.device != dev or tab.dim() != 2 or not tab.is_contiguous() or not 1 <= tab.shape[1] <= abi.MAX_HEATBATH_TABLE:
+            raise ValueError("a table on the device is a contiguous int32 tensor [n_sweeps][table_len <= 512] (device_table)")
+        n_sweeps = int(tab.shape[0])
+    else:
+        n_sweeps = int(np.asarray(betas).size)
+        tab = device_table(betas, dev)
+    if isinstance(seeds, torch.Tensor):
+        if seeds.dtype != torch.int32 or seeds.device != dev or not seeds.is_contiguous() or tuple(seeds.shape) != (n,):
+            raise ValueError("seeds must be a contiguous int32 tensor [n_chains] on the device of states (the uint32 seeds bit for bit)")
+    else:
+        seeds = _upload(_host_seeds(seeds, n).view(np.int32), dev)
+    if out is None:
+        out = torch.empty_like(states)
+    elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
+    res = {"state": out}
+    tdt = {np.int32: torch.int32, np.int64: torch.int64}
+    for k, dt in dtypes.items():
+        res[k] = torch.empty(n, dtype=tdt[dt], device=dev)
+    if best_state:
+        res["best_state"] = torch.empty_like(states)
+    if trace:
+        res["energy_hist"] = torch.empty((n, n_sweeps + 1), dtype=torch.int32, device=dev)
+    return tab, n_sweeps, seeds, res
+
+
+def _point(q, states, seeds, tab, res, dtypes, n_sweeps):
+    """The device pointers of a call into its parameter block."""
+    q.seeds, q.table, q.state_in, q.state_out = seeds.data_ptr(), tab.data_ptr(), states.data_ptr(), res["state"].data_ptr()
+    for k in tuple(dtypes) + ("best_state", "energy_hist"):
+        if k in res:
+            setattr(q, k, res[k].data_ptr())
+    q.hist_stride = n_sweeps + 1
+
+
 def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=False, best_state=True, stream=None):
     """mcq_heatbath_device on a torch uint8 tensor [n_chains][N*N] of the current device, enqueued on `stream` (default: torch's current
     stream).  Asynchronous: nothing is copied back and nothing synchronises, so the results are valid once the stream has passed the
@@ -85,37 +135,9 @@ def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=Fals
     dev = states.device
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.device(dev), torch.cuda.stream(st):
-        if isinstance(betas, torch.Tensor):  # the rows of device_table, already on the device
-            tab = betas
-            if tab.dtype != torch.int32 or tab.device != dev or tab.dim() != 2 or not tab.is_contiguous() or not 1 <= tab.shape[1] <= abi.MAX_HEATBATH_TABLE:
-                raise ValueError("a table on the device is a contiguous int32 tensor [n_sweeps][table_len <= 512] (device_table)")
-            n_sweeps = int(tab.shape[0])
-        else:
-            n_sweeps = int(np.asarray(betas).size)
-            tab = device_table(betas, dev)
-        if isinstance(seeds, torch.Tensor):
-            if seeds.dtype != torch.int32 or seeds.device != dev or not seeds.is_contiguous() or tuple(seeds.shape) != (n,):
-                raise ValueError("seeds must be a contiguous int32 tensor [n_chains] on the device of states (the uint32 seeds bit for bit)")
-        else:
-            seeds = _upload(_host_seeds(seeds, n).view(np.int32), dev)
-        if out is None:
-            out = torch.empty_like(states)
-        elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
-        res = {"state": out}
-        tdt = {np.int32: torch.int32, np.int64: torch.int64}
-        for k, dt in abi.HEATBATH_DTYPES.items():
-            res[k] = torch.empty(n, dtype=tdt[dt], device=dev)
-        if best_state:
-            res["best_state"] = torch.empty_like(states)
-        if trace:
-            res["energy_hist"] = torch.empty((n, n_sweeps + 1), dtype=torch.int32, device=dev)
+        tab, n_sweeps, seeds, res = _device_buffers(states, seeds, betas, out, abi.HEATBATH_DTYPES, trace, best_state)
         q = _block(N, n, n_sweeps, first_sweep, tab)
-        q.seeds, q.table, q.state_in, q.state_out = seeds.data_ptr(), tab.data_ptr(), states.data_ptr(), out.data_ptr()
-        for k in tuple(abi.HEATBATH_DTYPES) + ("best_state", "energy_hist"):
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
-        q.hist_stride = n_sweeps + 1
+        _point(q, states, seeds, tab, res, abi.HEATBATH_DTYPES, n_sweeps)
         _lib.heatbath_device(q, st)
         seeds.record_stream(st), tab.record_stream(st)  # (the kernel reads them after this call has returned)
     return res
@@ -146,6 +168,84 @@ def heatbath_states(N, states, seeds, betas, first_sweep=0, trace=False):
     return to_numpy(res)
 
 
+def _block3d(N, Q, n, n_sweeps, first_sweep, table):
+    q = abi.Heatbath3D()
+    q.N, q.n_queens, q.n_chains, q.n_sweeps, q.first_sweep = int(N), int(Q), int(n), int(n_sweeps), int(first_sweep)
+    q.table_len = int(table.shape[1])
+    return q
+
+
+def heatbath_queens_host(N, states, seeds, betas, Q=None, first_sweep=0, trace=False):
+    """mcq_heatbath3d_host: the full_3d rule in the library's plain host code, NumPy in and out, no GPU.  Same result as heatbath_queens."""
+    s = _host_queens(N, states, Q)
+    n, Qn = s.shape[0], _queens_of(N, Q)
+    seeds = _host_seeds(seeds, n)
+    table = abi.heatbath_table(betas)
+    n_sweeps = int(np.asarray(betas).size)
+    out = {"state": np.zeros_like(s), "best_state": np.zeros_like(s)}
+    for k, dt in abi.HEATBATH3D_DTYPES.items():
+        out[k] = np.zeros(n, dtype=dt)
+    q = _block3d(N, Qn, n, n_sweeps, first_sweep, table)
+    q.seeds, q.table = seeds.ctypes.data, table.ctypes.data
+    q.state_in, q.state_out, q.best_state = s.ctypes.data, out["state"].ctypes.data, out["best_state"].ctypes.data
+    for k in abi.HEATBATH3D_DTYPES:
+        setattr(q, k, out[k].ctypes.data)
+    if trace:
+        out["energy_hist"] = np.zeros((n, n_sweeps + 1), dtype=np.int32)
+        q.energy_hist, q.hist_stride = out["energy_hist"].ctypes.data, n_sweeps + 1
+    _lib.heatbath3d_host(q)
+    return out
+
+
+def heatbath_queens_device(N, states, seeds, betas, Q=None, first_sweep=0, out=None, trace=False, best_state=True, stream=None):
+    """mcq_heatbath3d_device on a torch uint8 tensor [n_chains][3 Q] or [n_chains][Q][3] of the current device (the final_state layout of
+    a full_3d run; Q=None means N^2), enqueued on `stream` (default: torch's current stream).  Asynchronous: nothing is copied back and
+    nothing synchronises.  `seeds`, `betas` and `out` are those of heatbath_device: tensors already on the device or host values that are
+    uploaded on the stream; `out` may be `states` itself (in place).  Returns a dict of tensors: `state` like `states`, `energy_in`,
+    `energy_out`, `best_energy`, `flags` int32[n_chains], `best_sweep`, `n_changed` int64[n_chains], `best_state` unless
+    best_state=False, and with trace=True `energy_hist` int32[n_chains][n_sweeps + 1]."""
+    import torch
+
+    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
+        raise ValueError("heatbath_queens_device takes a contiguous uint8 tensor on the GPU")
+    Qn = _queens_of(N, Q)
+    ok = (states.dim() == 2 and int(states.shape[1]) == 3 * Qn) or (states.dim() == 3 and tuple(states.shape[1:]) == (Qn, 3))
+    if states.dim() not in (2, 3) or (abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and Qn >= 2 and not ok):
+        raise ValueError(f"states must be uint8[n_chains][{3 * Qn}] or [n_chains][{Qn}][3] (final_state layout of full_3d), got {tuple(states.shape)}")
+    n = int(states.shape[0])
+    dev = states.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        tab, n_sweeps, seeds, res = _device_buffers(states, seeds, betas, out, abi.HEATBATH3D_DTYPES, trace, best_state)
+        q = _block3d(N, Qn, n, n_sweeps, first_sweep, tab)
+        _point(q, states, seeds, tab, res, abi.HEATBATH3D_DTYPES, n_sweeps)
+        _lib.heatbath3d_device(q, st)
+        seeds.record_stream(st), tab.record_stream(st)  # (the kernel reads them after this call has returned)
+    return res
+
+
+def heatbath_queens(N, states, seeds, betas, Q=None, first_sweep=0, trace=False):
+    """Heat-bath sweeps of full_3d placements on the GPU: `states` is uint8[n_chains][3 Q] or [n_chains][Q][3] (Q triples (i, j, k);
+    Q=None means N^2), bytes >= N are clamped to N - 1; `seeds` one uint32 per chain; `betas` one beta >= 0 per sweep.  Returns a dict of
+    NumPy arrays with the keys of FIELDS_3D: `state` uint8[n_chains][3 Q], `energy_in` (the energy of the input, recounted on the
+    device), `energy_out`, `best_energy`, `best_sweep`, `best_state`, `n_changed` (updates that changed a cell, of len(betas) Q) and
+    `flags` (bit 0, abi.HEATBATH3D_REPEATED: an input with two queens in one cell, which is recounted and handed back unmoved), and with
+    trace=True `energy_hist` int32[n_chains][len(betas) + 1].  ValueError for what the library refuses (N outside 2 .. 32, Q outside
+    2 .. N^3 - 1, no chain, a negative first_sweep, ...) and for a negative beta."""
+    import torch
+
+    s = _host_queens(N, states, Q)
+    if s.shape[0] == 0:
+        abi.heatbath_table(betas)
+        _lib.heatbath3d_host(_block3d(N, _queens_of(N, Q), 0, 0, first_sweep, abi.heatbath_table([])))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = heatbath_queens_device(N, torch.from_numpy(s).to(dev), seeds, betas, Q=Q, first_sweep=first_sweep, trace=trace)
+    torch.cuda.current_stream(dev).synchronize()
+    out = to_numpy(res)
+    out["state"], out["best_state"] = out["state"].reshape(s.shape), out["best_state"].reshape(s.shape)
+    return out
+
+
 def check(n_chains, n_sweeps, resample_every, population=None):
     """What anneal_heatbath does not resample, as ValueError before anything is launched -- population.check's refusals, for the same
     reasons, with steps read as sweeps.  Returns (S, R): the segment length in sweeps and the population size in force."""
@@ -162,7 +262,8 @@ def check(n_chains, n_sweeps, resample_every, population=None):
     return S, R
 
 
-def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=None, population=None, resample_seed=0, quench=False, trace=False):
+def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=None, population=None, resample_seed=0, quench=False, trace=False,
+                    mcmc_type="board", Q=None):
     """Every chain of `seeds` for n_sweeps heat-bath sweeps under one beta schedule, beta of sweep s = abi.beta_values(schedule_params,
     n_sweeps)[s] (the reference's schedules, evaluated per sweep instead of per step).
 
@@ -177,6 +278,11 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     only by a strictly lower energy), n_changed, `energy_hist` int32[n_chains][n_sweeps + 1] with trace=True (segments joined by dropping
     each later segment's entry 0, as anneal_population does), and with quench=True `quenched_state`, `quenched_energy`, `quench_moves`
     (best_state through quench.quench_device on the same stream).
+
+    mcmc_type="full_3d" (default "board": everything above) runs heat-bath QUEEN sweeps of Q queens in the cube (Q=None: N^2) through
+    heatbath_queens_device: the placements are uint8[n_chains][3 Q], the start placements those of start_chains(..., mcmc_type="full_3d")
+    or given ones, the segments, boundaries and fold are the same, `res` also holds `flags` (of the last segment), and quench=True goes
+    through quench.quench_queens_device.
 
     ValueError before anything is launched: a negative beta, and with resampling what anneal_population refuses for the same reasons -- a
     schedule that decreases over a segment, a resample_every <= 0, a population that does not divide the chains, is no multiple of 16 or
@@ -196,9 +302,23 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     n = len(seeds)
     beta = abi.beta_values(schedule_params, n_sweeps)
     abi.heatbath_table(beta[:1])  # a negative beta is refused here
-    if not (abi.MIN_N <= int(N) <= abi.MAX_N_BOARD):
-        raise ValueError(f"N out of range [{abi.MIN_N}, {abi.MAX_N_BOARD}]: {N}")
-    Q = int(N) * int(N)
+    if mcmc_type not in ("board", "full_3d"):
+        raise ValueError(f"Unknown mcmc_type {mcmc_type}")
+    cube = mcmc_type == "full_3d"
+    max_n = abi.MAX_N_QUENCH3D if cube else abi.MAX_N_BOARD
+    if not (abi.MIN_N <= int(N) <= max_n):
+        raise ValueError(f"N out of range [{abi.MIN_N}, {max_n}]: {N}")
+    if not cube and Q is not None:
+        raise ValueError("Q is the number of queens of a full_3d placement; a board has one height per column")
+    Qn = _queens_of(N, Q)
+    if cube and not 2 <= Qn <= int(N) ** 3 - 1:
+        raise ValueError(f"n_queens out of range [2, N^3 - 1 = {int(N) ** 3 - 1}] (0 = N^2): {Qn}")
+    Q = 3 * Qn if cube else int(N) * int(N)  # bytes of one placement
+    if cube:  # one segment of sweeps on the device, and the quench that goes with the placements
+        def sweep(*a, **kw):
+            return heatbath_queens_device(*a, Q=Qn, **kw)
+    else:
+        sweep = heatbath_device
     b = None
     if resample_every is not None:
         S, R = check(n, n_sweeps, resample_every, population)
@@ -214,10 +334,10 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
 
         if init not in abi.INIT:
             raise ValueError(f"Unknown init_mode {init}")
-        first, _ = _ex.start_chains(N, 0, init, schedule_params, seeds, mcmc_type="board", trace=False, states=True)
-        start = np.ascontiguousarray(first["final_state"], dtype=np.uint8)
+        first, _ = _ex.start_chains(N, 0, init, schedule_params, seeds, mcmc_type=mcmc_type, trace=False, states=True, Q=Qn if cube else None)
+        start = np.ascontiguousarray(first["final_state"], dtype=np.uint8).reshape(n, -1)
     else:
-        start = _host_states(N, init)
+        start = _host_queens(N, init, Qn) if cube else _host_states(N, init)
     if start.shape != (n, Q):
         raise ValueError(f"init must be uint8[{n}][{Q}] (one placement per seed), got {start.shape}")
 
@@ -232,7 +352,7 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         hist = i32(n, n_sweeps + 1) if trace else None
         quenched = None
         if b is None:
-            seg = heatbath_device(N, state, dseeds, dtab if n_sweeps else [], first_sweep=0, out=state, trace=trace, stream=st)  # one call, in place
+            seg = sweep(N, state, dseeds, dtab if n_sweeps else [], first_sweep=0, out=state, trace=trace, stream=st)  # one call, in place
             hist = seg.get("energy_hist")
             acc = {"best_energy": seg["best_energy"], "steps_to_best": seg["best_sweep"], "n_accepted": seg["n_changed"], "best_state": seg["best_state"]}
             e0, e1 = seg["energy_in"], seg["energy_out"]
@@ -250,7 +370,7 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
             done = 0
             keep = []
             for k, L in enumerate(lengths):
-                seg = heatbath_device(N, state, dseeds, dtab[done: done + L], first_sweep=done, out=final, trace=trace, stream=st)
+                seg = sweep(N, state, dseeds, dtab[done: done + L], first_sweep=done, out=final, trace=trace, stream=st)
                 keep.append(seg)
                 seg_e0[k].copy_(seg["energy_in"]), seg_e1[k].copy_(seg["energy_out"])
                 r = abi.Resample()
@@ -277,12 +397,17 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         if quench:  # behind the last fold, which has written acc["best_state"]; same stream, nothing waited for
             from . import quench as _quench
 
-            quenched = _quench.quench_device(N, acc["best_state"], conflicts=False, stream=st)
+            if cube:
+                quenched = _quench.quench_queens_device(N, acc["best_state"], Q=Qn, conflicts=False, stream=st)
+            else:
+                quenched = _quench.quench_device(N, acc["best_state"], conflicts=False, stream=st)
         st.synchronize()
 
     res = {"initial_energy": e0.cpu().numpy(), "final_energy": e1.cpu().numpy(), "final_state": state.cpu().numpy(),
            "best_energy": acc["best_energy"].cpu().numpy(), "best_sweep": acc["steps_to_best"].cpu().numpy(),
            "best_state": acc["best_state"].cpu().numpy(), "n_changed": acc["n_accepted"].cpu().numpy()}
+    if cube:
+        res["flags"] = seg["flags"].cpu().numpy()
     if trace:
         res["energy_hist"] = hist.cpu().numpy()
     if quenched is not None:
