@@ -530,7 +530,7 @@ typedef struct mcq_heatbath {
     int64_t hist_stride;   /* int32 entries per chain row of energy_hist, >= n_sweeps + 1 (read only when energy_hist is given) */
 } mcq_heatbath;
 
-/* the message of the last error of the calling thread from the two mcq_heatbath_* calls below (they do not set mcq_last_error()) */
+/* the message of the last error of the calling thread from the mcq_heatbath_* calls below (they do not set mcq_last_error()) */
 const char* mcq_heatbath_last_error(void);
 /* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`; asynchronous: nothing is copied back and nothing
  * synchronises.  MCQ_EINVAL before any launch: mode other than board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative
@@ -540,6 +540,18 @@ const char* mcq_heatbath_last_error(void);
 int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
 int mcq_heatbath_host(const mcq_heatbath* q);
+/* The counter form of the same sweep for N <= MCQ_MAX_N_HEATBATH_COUNTERS: the same parameter block, the same refusals and the same
+ * asynchrony as mcq_heatbath_device, and MCQ_EINVAL before any launch for a larger N (mcq_heatbath_device runs every N).  Its outputs
+ * equal those of mcq_heatbath_device and of mcq_heatbath_host bit for bit: the rule above is one rule, and only the way a(c, k) is
+ * obtained differs.  Take the 12 line families of the cube with in-plane direction (0,1), (1,0), (1,1), (1,-1) and height step 0, +1,
+ * -1 per cell, and let cnt_f(l) be the number of queens of the (clamped) board on line l of family f (at most N, a byte).  Then for a
+ * column c = (i, j) of height h(c) and every k
+ *     a(c, k) = sum over f of cnt_f(the line of family f through (i, j, k)) - 12 [k = h(c)]:
+ * the column's own queen lies on all 12 lines through (i, j, h(c)) and on none of the 12 through another cell of its column.  The
+ * kernel keeps the counters in LDS in place of the cells: 12 byte reads per height, and 12 decrements and 12 increments where a drawn
+ * height differs from the old one. */
+#define MCQ_MAX_N_HEATBATH_COUNTERS 16
+int mcq_heatbath_counters_device(const mcq_heatbath* q, void* hip_stream);
 
 /*
  * Quench of full_3d placements: the deterministic zero-temperature descent of Q queens in the N^3 cube to a local minimum under

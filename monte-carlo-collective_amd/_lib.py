@@ -188,6 +188,8 @@ def lib():
         L.mcq_heatbath_last_error.restype = C.c_char_p
         L.mcq_heatbath_device.restype = C.c_int
         L.mcq_heatbath_device.argtypes = [C.POINTER(abi.Heatbath), C.c_void_p]
+        L.mcq_heatbath_counters_device.restype = C.c_int
+        L.mcq_heatbath_counters_device.argtypes = [C.POINTER(abi.Heatbath), C.c_void_p]
         L.mcq_heatbath_host.restype = C.c_int
         L.mcq_heatbath_host.argtypes = [C.POINTER(abi.Heatbath)]
         L.mcq_quench3d_last_error.restype = C.c_char_p
@@ -261,6 +263,12 @@ def heatbath_host(q):
 def heatbath_device(q, stream):
     """mcq_heatbath_device on a filled abi.Heatbath block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_heatbath(lib().mcq_heatbath_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def heatbath_counters_device(q, stream):
+    """mcq_heatbath_counters_device (the counter form, N <= abi.MAX_N_HEATBATH_COUNTERS) on a filled abi.Heatbath block of DEVICE pointers,
+    enqueued on the torch stream `stream`; asynchronous."""
+    _check_heatbath(lib().mcq_heatbath_counters_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def quench_host(q):

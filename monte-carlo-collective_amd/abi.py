@@ -193,6 +193,7 @@ QUENCH3D_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.
 
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
+MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device
 
 
 class Heatbath(C.Structure):

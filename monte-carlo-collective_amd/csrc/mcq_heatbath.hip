@@ -268,7 +268,144 @@ __global__ __launch_bounds__(64) void mcq_heatbath_kernel(HeatbathArgs a) {
     }
 }
 
-// what both entry points refuse
+// ---- the counter form, N <= MCQ_MAX_N_HEATBATH_COUNTERS (include/mcq.h: mcq_heatbath_counters_device) ----
+// The same walk with the cells of a column never looked at.  The 12 line families of the cube that matter -- in-plane direction (0,1),
+// (1,0), (1,1), (1,-1), height step 0, +1, -1 per cell along the line -- keep one byte each per line: the number of queens on it.
+//   a(c, k) = the sum over the 12 families of the counter of the line through (i, j, k)  -  12 [k = h(c)]
+// (the column's own queen lies on all 12 lines through its cell and on none through another cell of its column).  A counter is at
+//   line (5N - 2) + v,   line = i | N + j | 3N - 1 + i - j | 4N - 1 + i + j   (6N - 2 lines in the plane),
+//                        v = k | 2N - 1 - pos + k | 3N - 1 + pos + k          (height step 0, +1, -1; pos = j along a row, i otherwise),
+// so the lanes of a group, the heights k, read 16 consecutive bytes per family.  A chain's region holds these (6N - 2)(5N - 2) bytes
+// and ONE copy of the heights; regions are 64 bytes off a multiple of 128, so that the two chains of a half-wavefront read different
+// banks.  The counters are built once from the clamped input with 32-bit LDS atomics of 1 << 8 (byte in the dword): bytes of one dword
+// belong to different lines, and a counter stays within 0 .. N <= 16, so a byte neither carries nor borrows.  A changed height moves 24
+// counters before the next column is visited: lane f < 12 of the group owns family f and issues one atomic subtraction on the line
+// through the old cell and one addition on the line through the new one.  The chains of a wavefront diverge on "changed"; there is no
+// barrier inside that branch, and the LDS serves the instructions of one wavefront in their order, so the next column's reads see them.
+__device__ __forceinline__ int counter_offset(int dir, int step, int i, int j, int N) {
+    const int line = dir == 0 ? i : dir == 1 ? N + j : dir == 2 ? 3 * N - 1 + i - j : 4 * N - 1 + i + j;
+    const int pos = dir == 0 ? j : i;
+    const int v = step == 0 ? 0 : step == 1 ? 2 * N - 1 - pos : 3 * N - 1 + pos;
+    return line * (5 * N - 2) + v;
+}
+
+template <int NP>
+__global__ __launch_bounds__(64) void mcq_heatbath_counters_kernel(HeatbathArgs a) {
+    constexpr int GW = 16, CPW = 64 / GW;
+    constexpr int CNT = (6 * NP - 2) * (5 * NP - 2);                  // bytes of counters; a multiple of 4 for NP = 8, 12, 16
+    constexpr int CHAIN = (CNT + NP * NP + 63) / 128 * 128 + 64;       // bytes of a chain's region: >= CNT + NP^2, = 64 mod 128
+    static_assert(CNT % 4 == 0 && NP <= GW, "counter layout");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[CPW * CHAIN / 4];
+    __shared__ uint32_t tab[512];
+    const int N = a.N, Q = N * N, D = a.table_len;
+    const int lane = threadIdx.x & (GW - 1), grp = threadIdx.x / GW;
+    const long long chain = (long long)blockIdx.x * CPW + grp;
+    const bool valid = chain < a.n_chains;
+    const long long ch = valid ? chain : a.n_chains - 1;  // a group beyond the last chain walks the last chain and writes nothing
+    uint32_t* cw = lds + grp * (CHAIN / 4);
+    const uint8_t* cb = (const uint8_t*)cw;
+    uint8_t* hts = (uint8_t*)cw + CNT;
+    for (int w = lane; w < CNT / 4; w += GW) cw[w] = 0u;
+    __syncthreads();
+    const uint8_t* in = a.state_in + ch * Q;
+    for (int c = lane; c < Q; c += GW) {
+        const int v = in[c], i = c / N, j = c - i * N;
+        const int hv = v < N ? v : N - 1;
+        hts[c] = (uint8_t)hv;
+#pragma unroll
+        for (int f = 0; f < 12; f++) {
+            const int b = counter_offset(f / 3, f % 3, i, j, N) + hv;
+            atomicAdd(cw + (b >> 2), 1u << (8 * (b & 3)));
+        }
+    }
+    __syncthreads();
+    if (valid && a.best_state) {  // until a sweep end is strictly lower: the (clamped) input
+        uint8_t* out = a.best_state + ch * Q;
+        for (int c = lane; c < Q; c += GW) out[c] = hts[c];
+    }
+    const int k0 = lane, kr = min(lane, N - 1);  // a lane beyond N reads the counters of the last height and is left out below
+    const int own_dir = lane / 3, own_step = lane - 3 * own_dir;  // lane f < 12 updates family f
+    const uint32_t seed = a.seeds[ch];
+    int32_t* hist = a.energy_hist ? a.energy_hist + ch * a.hist_stride : nullptr;
+
+    int E = 0, e_in = 0, best = 0;
+    long long best_sweep = 0, changed = 0;
+    uint32_t rnd[4] = {0, 0, 0, 0};
+    // sweep -1 is the recount of the input: the same walk with no update
+    for (long long s = -1; s < a.n_sweeps; s++) {
+        const bool recount = s < 0;
+        if (!recount) {
+            __syncthreads();
+            const uint32_t* row = a.table + s * D;
+            for (int d = threadIdx.x; d < D; d += 64) tab[d] = row[d];
+            __syncthreads();
+        }
+        const unsigned long long w0 = recount ? 0ull : (unsigned long long)(a.first_sweep + s) * (unsigned long long)Q;
+        int twoE = 0;
+        for (int i = 0, c = 0; i < N; i++)
+            for (int j = 0; j < N; j++, c++) {
+                int c0 = 0;
+#pragma unroll
+                for (int f = 0; f < 12; f++) c0 += cb[counter_offset(f / 3, f % 3, i, j, N) + kr];
+                const int cur = hts[c];
+                c0 -= k0 == cur ? 12 : 0;
+                const int a_old = __shfl(c0, cur, GW);
+                if (recount) {
+                    twoE += a_old;
+                    continue;
+                }
+                const int a_min = group_min<GW>(k0 < N ? c0 : INT_MAX);
+                const uint32_t wt0 = k0 < N ? tab[min(c0 - a_min, D - 1)] : 0u;
+                uint32_t W;
+                const uint32_t C0 = group_scan<GW>(wt0, lane, W);
+                const unsigned long long w = w0 + (unsigned)c;
+                if ((w & 3) == 0 || c == 0) philox_block((uint32_t)(w >> 2), (uint32_t)(w >> 34), seed, 1u, rnd);
+                const int e = (int)(w & 3);
+                const uint32_t x = e == 0 ? rnd[0] : e == 1 ? rnd[1] : e == 2 ? rnd[2] : rnd[3];
+                const uint32_t U = __umulhi(x, W);
+                // the smallest k with C_k > U = the number of heights with C_k <= U (C is non-decreasing; a lane beyond N holds W > U)
+                int kn = __popcll((__ballot(C0 <= U) >> (grp * GW)) & ((1ull << GW) - 1));
+                kn = min(kn, N - 1);  // (only a table with T[0] = 0, W = 0, gets here: the last height, as in the host code)
+                const int a_new = __shfl(c0, kn, GW);
+                E += a_new - a_old;
+                changed += kn != cur;
+                if (kn != cur && lane < 12) {
+                    const int o = counter_offset(own_dir, own_step, i, j, N);
+                    const int b0 = o + cur, b1 = o + kn;
+                    atomicSub(cw + (b0 >> 2), 1u << (8 * (b0 & 3)));
+                    atomicAdd(cw + (b1 >> 2), 1u << (8 * (b1 & 3)));
+                }
+                hts[c] = (uint8_t)kn;  // by every lane of the group: same address, same value
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (no instruction: the compiler keeps the next column's reads behind the updates)
+            }
+        if (recount) {
+            E = e_in = best = twoE >> 1;
+            if (valid && hist && lane == 0) hist[0] = E;
+            continue;
+        }
+        if (valid && hist && lane == 0) hist[s + 1] = E;
+        if (E < best) {
+            best = E;
+            best_sweep = s + 1;
+            if (valid && a.best_state) {
+                uint8_t* out = a.best_state + ch * Q;
+                for (int c = lane; c < Q; c += GW) out[c] = hts[c];
+            }
+        }
+    }
+    if (!valid) return;
+    uint8_t* out = a.state_out + ch * Q;
+    for (int c = lane; c < Q; c += GW) out[c] = hts[c];
+    if (lane == 0) {
+        if (a.energy_in) a.energy_in[ch] = e_in;
+        if (a.energy_out) a.energy_out[ch] = E;
+        if (a.best_energy) a.best_energy[ch] = best;
+        if (a.best_sweep) a.best_sweep[ch] = best_sweep;
+        if (a.n_changed) a.n_changed[ch] = changed;
+    }
+}
+
+// what every entry point refuses
 int check_heatbath(const mcq_heatbath* q) {
     if (!q) return heatbath_fail(MCQ_EINVAL, "mcq_heatbath: NULL parameter block");
     if (q->mode != MCQ_MODE_BOARD) return heatbath_fail(MCQ_EINVAL, "mode: the heat-bath sweep runs boards only (MCQ_MODE_BOARD), got %d", (int)q->mode);
@@ -294,6 +431,17 @@ template <int GW, int KPL, int NP>
 void launch_heatbath(const HeatbathArgs& a, hipStream_t s) {
     constexpr int CPW = 64 / GW;
     hipLaunchKernelGGL((mcq_heatbath_kernel<GW, KPL, NP>), dim3((unsigned)((a.n_chains + CPW - 1) / CPW)), dim3(64), 0, s, a);
+}
+
+template <int NP>
+void launch_heatbath_counters(const HeatbathArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL((mcq_heatbath_counters_kernel<NP>), dim3((unsigned)((a.n_chains + 3) / 4)), dim3(64), 0, s, a);
+}
+
+HeatbathArgs heatbath_args(const mcq_heatbath* q) {
+    return HeatbathArgs{q->seeds, q->table, q->state_in, q->state_out, q->energy_in, q->energy_out, q->best_energy, q->best_sweep, q->best_state,
+                        q->n_changed, q->energy_hist, (long long)q->hist_stride, (long long)q->n_chains, (long long)q->n_sweeps,
+                        (long long)q->first_sweep, (int)q->table_len, (int)q->N};
 }
 
 // a[k] = a(c, k) of column (i, j), k = 0 .. N - 1 (the quench's rule, items 1 - 2)
@@ -391,9 +539,7 @@ int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream) {
     const int rc = check_heatbath(q);
     if (rc != MCQ_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    const HeatbathArgs a{q->seeds, q->table, q->state_in, q->state_out, q->energy_in, q->energy_out, q->best_energy, q->best_sweep, q->best_state,
-                         q->n_changed, q->energy_hist, (long long)q->hist_stride, (long long)q->n_chains, (long long)q->n_sweeps,
-                         (long long)q->first_sweep, (int)q->table_len, (int)q->N};
+    const HeatbathArgs a = heatbath_args(q);
     const int N = q->N;
     if (N <= 8) launch_heatbath<16, 1, 8>(a, s);
     else if (N <= 12) launch_heatbath<16, 1, 12>(a, s);
@@ -404,6 +550,23 @@ int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream) {
     else launch_heatbath<64, 2, 128>(a, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return heatbath_fail(MCQ_EDEVICE, "mcq_heatbath_device: %s", hipGetErrorString(e));
+    return MCQ_OK;
+}
+
+int mcq_heatbath_counters_device(const mcq_heatbath* q, void* hip_stream) {
+    const int rc = check_heatbath(q);
+    if (rc != MCQ_OK) return rc;
+    if (q->N > MCQ_MAX_N_HEATBATH_COUNTERS)
+        return heatbath_fail(MCQ_EINVAL, "N = %d: the counter form of the heat-bath sweep runs N <= %d (MCQ_MAX_N_HEATBATH_COUNTERS); mcq_heatbath_device runs every N",
+                             (int)q->N, MCQ_MAX_N_HEATBATH_COUNTERS);
+    hipStream_t s = (hipStream_t)hip_stream;
+    const HeatbathArgs a = heatbath_args(q);
+    const int N = q->N;
+    if (N <= 8) launch_heatbath_counters<8>(a, s);
+    else if (N <= 12) launch_heatbath_counters<12>(a, s);
+    else launch_heatbath_counters<16>(a, s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return heatbath_fail(MCQ_EDEVICE, "mcq_heatbath_counters_device: %s", hipGetErrorString(e));
     return MCQ_OK;
 }
 

@@ -245,7 +245,7 @@ def write_best_heights(heights, N, path):
 
 def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.0, base_seed=42, init_mode="random",
                     out_dir="competition_results", runner=None, timestamp=None, resample_every=None, population=None, resample_seed=0, quench=False,
-                    heatbath_sweeps=None):
+                    heatbath_sweeps=None, heatbath_form="lines"):
     """competition.py:143-187: board chains with linear annealing beta_start -> beta_end, seeds base_seed + r; the board
     of the run with the lowest best energy is written to {out_dir}/best_heights_{N}_{timestamp}.txt.
     Returns (best energy, heights, path).
@@ -262,13 +262,15 @@ def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.
 
     heatbath_sweeps (not in the reference; None = nothing changes): the board comes from that many heat-bath column sweeps per run
     (heatbath.anneal_heatbath) instead of n_steps Metropolis steps, beta_start -> beta_end over the sweeps, from the same initial
-    placements; resample_every (then in sweeps), population, resample_seed and quench are honoured; `n_steps` and `runner` are unused."""
+    placements; resample_every (then in sweeps), population, resample_seed and quench are honoured; `n_steps` and `runner` are unused.
+    heatbath_form ("lines" or "counters", N <= 16) is anneal_heatbath's `form`: the kernel of the sweeps, not their result; unused
+    without heatbath_sweeps."""
     sp = {"type": "linear_annealing", "beta_start": beta_start, "beta_end": beta_end}
     if heatbath_sweeps is not None:
         from . import heatbath as _hb
 
         res = _hb.anneal_heatbath(N, heatbath_sweeps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), resample_every=resample_every,
-                                  population=population, resample_seed=resample_seed, quench=quench)
+                                  population=population, resample_seed=resample_seed, quench=quench, form=heatbath_form)
         return _write_competition(res[0] if resample_every is not None else res, N, out_dir, timestamp, quench)
     if resample_every is not None:
         from . import population as _pop

@@ -18,6 +18,17 @@ from .quench import _host_queens, _host_states, _queens_of
 
 FIELDS = ("state", "energy_in", "energy_out", "best_energy", "best_sweep", "best_state", "n_changed")
 FIELDS_3D = FIELDS + ("flags",)
+# the two kernels of the board sweep: "lines" (mcq_heatbath_device, every N, the default) tests the cells of a column's four lines;
+# "counters" (mcq_heatbath_counters_device, N <= abi.MAX_N_HEATBATH_COUNTERS) reads per-line queen counters.  Same rule, same results.
+FORMS = ("lines", "counters")
+
+
+def _check_form(form, N):
+    """ValueError for an unknown form and for the counter form beyond its largest N; nothing here touches the GPU."""
+    if form not in FORMS:
+        raise ValueError(f"Unknown form {form!r}: the heat-bath sweep of boards has the forms {FORMS}")
+    if form == "counters" and int(N) > abi.MAX_N_HEATBATH_COUNTERS:
+        raise ValueError(f'form="counters" runs N <= {abi.MAX_N_HEATBATH_COUNTERS}, got N = {int(N)}; form="lines" runs every N')
 
 
 def _block(N, n, n_sweeps, first_sweep, table):
@@ -116,7 +127,7 @@ def _point(q, states, seeds, tab, res, dtypes, n_sweeps):
     q.hist_stride = n_sweeps + 1
 
 
-def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=False, best_state=True, stream=None):
+def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=False, best_state=True, stream=None, form="lines"):
     """mcq_heatbath_device on a torch uint8 tensor [n_chains][N*N] of the current device, enqueued on `stream` (default: torch's current
     stream).  Asynchronous: nothing is copied back and nothing synchronises, so the results are valid once the stream has passed the
     call.  `seeds` is an int32 tensor [n_chains] on the device holding the uint32 seeds bit for bit (or a NumPy array / list, which is
@@ -124,7 +135,9 @@ def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=Fals
     stream through a pinned copy) or is device_table's tensor, or a slice of its rows.  `out` (optional) is the tensor the placements go to; it may be `states` itself (in place), default a new one.
     Returns a dict of tensors: `state`, `energy_in` (the recount of the input), `energy_out`, `best_energy` int32[n_chains],
     `best_sweep`, `n_changed` int64[n_chains], `best_state` unless best_state=False, and with trace=True `energy_hist`
-    int32[n_chains][n_sweeps + 1]."""
+    int32[n_chains][n_sweeps + 1].  `form` is one of FORMS: "counters" runs mcq_heatbath_counters_device (N <= 16; the same results bit
+    for bit); an unknown form, or "counters" with a larger N, is a ValueError before anything else is looked at."""
+    _check_form(form, N)
     import torch
 
     if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
@@ -138,7 +151,7 @@ def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=Fals
         tab, n_sweeps, seeds, res = _device_buffers(states, seeds, betas, out, abi.HEATBATH_DTYPES, trace, best_state)
         q = _block(N, n, n_sweeps, first_sweep, tab)
         _point(q, states, seeds, tab, res, abi.HEATBATH_DTYPES, n_sweeps)
-        _lib.heatbath_device(q, st)
+        (_lib.heatbath_counters_device if form == "counters" else _lib.heatbath_device)(q, st)
         seeds.record_stream(st), tab.record_stream(st)  # (the kernel reads them after this call has returned)
     return res
 
@@ -148,14 +161,16 @@ def to_numpy(res):
     return {k: t.cpu().numpy() for k, t in res.items()}
 
 
-def heatbath_states(N, states, seeds, betas, first_sweep=0, trace=False):
+def heatbath_states(N, states, seeds, betas, first_sweep=0, trace=False, form="lines"):
     """Heat-bath sweeps of board placements on the GPU: `states` is uint8[n_chains][N*N] (the final_state / best_state layout; one board
     of N*N heights is taken as one chain), bytes >= N are clamped to N - 1; `seeds` one uint32 per chain; `betas` one beta >= 0 per
     sweep (len(betas) sweeps are run, with the global indices first_sweep, first_sweep + 1, ...).  Returns a dict of NumPy arrays:
     `state` (the placements after the sweeps), `energy_in` (the energy of the input, recounted on the device), `energy_out`,
     `best_energy`, `best_sweep` (sweeps of this call after which best_energy was first reached; 0 = the input), `best_state`,
     `n_changed` (updates that changed a height, of len(betas) N^2) and with trace=True `energy_hist` int32[n_chains][len(betas) + 1].
-    ValueError for what the library refuses (N outside 2 .. 128, no chain, a negative first_sweep, ...) and for a negative beta."""
+    ValueError for what the library refuses (N outside 2 .. 128, no chain, a negative first_sweep, ...) and for a negative beta.
+    `form` is heatbath_device's: "lines" or "counters" (N <= 16), the same results."""
+    _check_form(form, N)
     import torch
 
     s = _host_states(N, states)
@@ -163,7 +178,7 @@ def heatbath_states(N, states, seeds, betas, first_sweep=0, trace=False):
         abi.heatbath_table(betas)
         _lib.heatbath_host(_block(N, 0, 0, first_sweep, abi.heatbath_table([])))  # raises the library's refusal
     dev = torch.device("cuda", torch.cuda.current_device())
-    res = heatbath_device(N, torch.from_numpy(s).to(dev), seeds, betas, first_sweep=first_sweep, trace=trace)
+    res = heatbath_device(N, torch.from_numpy(s).to(dev), seeds, betas, first_sweep=first_sweep, trace=trace, form=form)
     torch.cuda.current_stream(dev).synchronize()
     return to_numpy(res)
 
@@ -263,7 +278,7 @@ def check(n_chains, n_sweeps, resample_every, population=None):
 
 
 def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=None, population=None, resample_seed=0, quench=False, trace=False,
-                    mcmc_type="board", Q=None):
+                    mcmc_type="board", Q=None, form="lines"):
     """Every chain of `seeds` for n_sweeps heat-bath sweeps under one beta schedule, beta of sweep s = abi.beta_values(schedule_params,
     n_sweeps)[s] (the reference's schedules, evaluated per sweep instead of per step).
 
@@ -284,9 +299,15 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     or given ones, the segments, boundaries and fold are the same, `res` also holds `flags` (of the last segment), and quench=True goes
     through quench.quench_queens_device.
 
-    ValueError before anything is launched: a negative beta, and with resampling what anneal_population refuses for the same reasons -- a
+    form (one of FORMS, default "lines") is the kernel every board segment runs through (heatbath_device's `form`; the results do not
+    depend on it); "counters" needs N <= 16, and full_3d placements have the one form "lines".
+
+    ValueError before anything is launched: an unknown form or one the placements do not have, a negative beta, and with resampling what anneal_population refuses for the same reasons -- a
     schedule that decreases over a segment, a resample_every <= 0, a population that does not divide the chains, is no multiple of 16 or
     exceeds 2^19."""
+    if mcmc_type == "full_3d" and form != "lines":
+        raise ValueError(f'the heat-bath queen sweep of full_3d placements has the one form "lines", got form={form!r}')
+    _check_form(form, N)
     import ctypes as C
 
     import torch
@@ -318,7 +339,8 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         def sweep(*a, **kw):
             return heatbath_queens_device(*a, Q=Qn, **kw)
     else:
-        sweep = heatbath_device
+        def sweep(*a, **kw):
+            return heatbath_device(*a, form=form, **kw)
     b = None
     if resample_every is not None:
         S, R = check(n, n_sweeps, resample_every, population)
