@@ -13,7 +13,10 @@ SOURCES = [os.path.join(CSRC, "mcq_hip.hip"), os.path.join(CSRC, "mcq_resume.hip
 # the heat-bath queen sweep of full_3d placements, built into the same library.  It is listed apart: SOURCES names the six files whose
 # device code earlier changes pinned (tests/test_quench3d_host.py counts them), and this file is compiled next to them, never into them
 ADDED_SOURCES = [os.path.join(CSRC, "mcq_heatbath3d.hip")]
-HEADERS = [os.path.join(os.path.dirname(HERE), "include", "mcq.h"), os.path.join(CSRC, "mcq_record.h")]
+# what the sources include: the C-ABI; the chain record of the sweep and the resume kernels; the attack field of the two full_3d files;
+# what the four files outside the sweep (the quenches and the heat baths) share beyond it
+HEADERS = [os.path.join(os.path.dirname(HERE), "include", "mcq.h"), os.path.join(CSRC, "mcq_record.h"), os.path.join(CSRC, "mcq_field.h"),
+           os.path.join(CSRC, "mcq_post.h")]
 HEADER = HEADERS[0]
 # -ffp-contract=off: the reference's schedule / acceptance expressions are evaluated without
 # fused multiply-adds (hipcc's default would contract beta_start + frac * delta into an FMA).

@@ -20,35 +20,18 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "../../include/mcq.h"
+#include "mcq_post.h"
 
 namespace {
 
+using mcq_post::fail;
+using mcq_post::host_counts;
+using mcq_post::philox_block;
+
 thread_local char g_heatbath_err[256] = "";
-
-int heatbath_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_heatbath_err, sizeof g_heatbath_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// philox4x32-10: counter (c0, c1, 0, 0), key (k0, k1)
-__host__ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t out[4]) {
-    uint32_t c2 = 0, c3 = 0;
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
-}
 
 struct HeatbathArgs {
     const uint32_t* seeds;
@@ -260,11 +243,7 @@ __global__ __launch_bounds__(64) void mcq_heatbath_kernel(HeatbathArgs a) {
         out[c] = rows[i * NP + (c - i * N)];
     }
     if (lane == 0) {
-        if (a.energy_in) a.energy_in[ch] = e_in;
-        if (a.energy_out) a.energy_out[ch] = E;
-        if (a.best_energy) a.best_energy[ch] = best;
-        if (a.best_sweep) a.best_sweep[ch] = best_sweep;
-        if (a.n_changed) a.n_changed[ch] = changed;
+        mcq_post::store_heatbath_figures(a, ch, e_in, E, best, best_sweep, changed);
     }
 }
 
@@ -397,33 +376,29 @@ __global__ __launch_bounds__(64) void mcq_heatbath_counters_kernel(HeatbathArgs 
     uint8_t* out = a.state_out + ch * Q;
     for (int c = lane; c < Q; c += GW) out[c] = hts[c];
     if (lane == 0) {
-        if (a.energy_in) a.energy_in[ch] = e_in;
-        if (a.energy_out) a.energy_out[ch] = E;
-        if (a.best_energy) a.best_energy[ch] = best;
-        if (a.best_sweep) a.best_sweep[ch] = best_sweep;
-        if (a.n_changed) a.n_changed[ch] = changed;
+        mcq_post::store_heatbath_figures(a, ch, e_in, E, best, best_sweep, changed);
     }
 }
 
 // what every entry point refuses
 int check_heatbath(const mcq_heatbath* q) {
-    if (!q) return heatbath_fail(MCQ_EINVAL, "mcq_heatbath: NULL parameter block");
-    if (q->mode != MCQ_MODE_BOARD) return heatbath_fail(MCQ_EINVAL, "mode: the heat-bath sweep runs boards only (MCQ_MODE_BOARD), got %d", (int)q->mode);
-    if (q->N < MCQ_MIN_N || q->N > MCQ_MAX_N_BOARD) return heatbath_fail(MCQ_EINVAL, "N out of range [%d, %d]: %d", MCQ_MIN_N, MCQ_MAX_N_BOARD, (int)q->N);
-    if (q->n_chains < 1 || q->n_chains > INT_MAX) return heatbath_fail(MCQ_EINVAL, "n_chains out of range [1, 2^31 - 1]: %lld", (long long)q->n_chains);
-    if (q->n_sweeps < 0) return heatbath_fail(MCQ_EINVAL, "n_sweeps must be >= 0, got %lld", (long long)q->n_sweeps);
-    if (q->first_sweep < 0) return heatbath_fail(MCQ_EINVAL, "first_sweep must be >= 0, got %lld", (long long)q->first_sweep);
+    if (!q) return fail(g_heatbath_err, MCQ_EINVAL, "mcq_heatbath: NULL parameter block");
+    if (q->mode != MCQ_MODE_BOARD) return fail(g_heatbath_err, MCQ_EINVAL, "mode: the heat-bath sweep runs boards only (MCQ_MODE_BOARD), got %d", (int)q->mode);
+    if (q->N < MCQ_MIN_N || q->N > MCQ_MAX_N_BOARD) return fail(g_heatbath_err, MCQ_EINVAL, "N out of range [%d, %d]: %d", MCQ_MIN_N, MCQ_MAX_N_BOARD, (int)q->N);
+    if (q->n_chains < 1 || q->n_chains > INT_MAX) return fail(g_heatbath_err, MCQ_EINVAL, "n_chains out of range [1, 2^31 - 1]: %lld", (long long)q->n_chains);
+    if (q->n_sweeps < 0) return fail(g_heatbath_err, MCQ_EINVAL, "n_sweeps must be >= 0, got %lld", (long long)q->n_sweeps);
+    if (q->first_sweep < 0) return fail(g_heatbath_err, MCQ_EINVAL, "first_sweep must be >= 0, got %lld", (long long)q->first_sweep);
     const uint64_t end = (uint64_t)q->first_sweep + (uint64_t)q->n_sweeps, Q = (uint64_t)q->N * (uint64_t)q->N;
     if (end > (uint64_t)INT64_MAX / Q)
-        return heatbath_fail(MCQ_EINVAL, "first_sweep + n_sweeps = %llu: the word index (first_sweep + n_sweeps) N^2 must stay below 2^63", (unsigned long long)end);
+        return fail(g_heatbath_err, MCQ_EINVAL, "first_sweep + n_sweeps = %llu: the word index (first_sweep + n_sweeps) N^2 must stay below 2^63", (unsigned long long)end);
     if (q->table_len < 1 || q->table_len > MCQ_MAX_HEATBATH_TABLE)
-        return heatbath_fail(MCQ_EINVAL, "table_len out of range [1, %d]: %lld", MCQ_MAX_HEATBATH_TABLE, (long long)q->table_len);
-    if (!q->seeds) return heatbath_fail(MCQ_EINVAL, "seeds is required");
-    if (!q->table && q->n_sweeps > 0) return heatbath_fail(MCQ_EINVAL, "table is required (n_sweeps rows of table_len words)");
-    if (!q->state_in) return heatbath_fail(MCQ_EINVAL, "state_in is required");
-    if (!q->state_out) return heatbath_fail(MCQ_EINVAL, "state_out is required");
+        return fail(g_heatbath_err, MCQ_EINVAL, "table_len out of range [1, %d]: %lld", MCQ_MAX_HEATBATH_TABLE, (long long)q->table_len);
+    if (!q->seeds) return fail(g_heatbath_err, MCQ_EINVAL, "seeds is required");
+    if (!q->table && q->n_sweeps > 0) return fail(g_heatbath_err, MCQ_EINVAL, "table is required (n_sweeps rows of table_len words)");
+    if (!q->state_in) return fail(g_heatbath_err, MCQ_EINVAL, "state_in is required");
+    if (!q->state_out) return fail(g_heatbath_err, MCQ_EINVAL, "state_out is required");
     if (q->energy_hist && q->hist_stride < q->n_sweeps + 1)
-        return heatbath_fail(MCQ_EINVAL, "hist_stride must be >= n_sweeps + 1 = %lld, got %lld", (long long)q->n_sweeps + 1, (long long)q->hist_stride);
+        return fail(g_heatbath_err, MCQ_EINVAL, "hist_stride must be >= n_sweeps + 1 = %lld, got %lld", (long long)q->n_sweeps + 1, (long long)q->hist_stride);
     return MCQ_OK;
 }
 
@@ -442,25 +417,6 @@ HeatbathArgs heatbath_args(const mcq_heatbath* q) {
     return HeatbathArgs{q->seeds, q->table, q->state_in, q->state_out, q->energy_in, q->energy_out, q->best_energy, q->best_sweep, q->best_state,
                         q->n_changed, q->energy_hist, (long long)q->hist_stride, (long long)q->n_chains, (long long)q->n_sweeps,
                         (long long)q->first_sweep, (int)q->table_len, (int)q->N};
-}
-
-// a[k] = a(c, k) of column (i, j), k = 0 .. N - 1 (the quench's rule, items 1 - 2)
-void host_counts(const uint8_t* h, int N, int i, int j, int* a) {
-    for (int k = 0; k < N; k++) a[k] = 0;
-    auto hit = [&](int hp, int d) {
-        a[hp]++;
-        if (hp - d >= 0) a[hp - d]++;
-        if (hp + d < N) a[hp + d]++;
-    };
-    for (int jj = 0; jj < N; jj++) {  // the row, and the two diagonal cells of board column jj
-        if (jj == j) continue;
-        const int d = jj > j ? jj - j : j - jj;
-        hit(h[i * N + jj], d);
-        if (i + d < N) hit(h[(i + d) * N + jj], d);
-        if (i - d >= 0) hit(h[(i - d) * N + jj], d);
-    }
-    for (int ii = 0; ii < N; ii++)  // the board column
-        if (ii != i) hit(h[ii * N + j], ii > i ? ii - i : i - ii);
 }
 
 }  // namespace
@@ -526,11 +482,7 @@ int mcq_heatbath_host(const mcq_heatbath* q) {
         }
         uint8_t* out = q->state_out + ch * Q;
         for (int c = 0; c < Q; c++) out[c] = h[(size_t)c];
-        if (q->energy_in) q->energy_in[ch] = e_in;
-        if (q->energy_out) q->energy_out[ch] = E;
-        if (q->best_energy) q->best_energy[ch] = best;
-        if (q->best_sweep) q->best_sweep[ch] = best_sweep;
-        if (q->n_changed) q->n_changed[ch] = changed;
+        mcq_post::store_heatbath_figures(*q, ch, e_in, E, best, best_sweep, changed);
     }
     return MCQ_OK;
 }
@@ -549,7 +501,7 @@ int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream) {
     else if (N <= 64) launch_heatbath<64, 1, 64>(a, s);
     else launch_heatbath<64, 2, 128>(a, s);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return heatbath_fail(MCQ_EDEVICE, "mcq_heatbath_device: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(g_heatbath_err, MCQ_EDEVICE, "mcq_heatbath_device: %s", hipGetErrorString(e));
     return MCQ_OK;
 }
 
@@ -557,7 +509,7 @@ int mcq_heatbath_counters_device(const mcq_heatbath* q, void* hip_stream) {
     const int rc = check_heatbath(q);
     if (rc != MCQ_OK) return rc;
     if (q->N > MCQ_MAX_N_HEATBATH_COUNTERS)
-        return heatbath_fail(MCQ_EINVAL, "N = %d: the counter form of the heat-bath sweep runs N <= %d (MCQ_MAX_N_HEATBATH_COUNTERS); mcq_heatbath_device runs every N",
+        return fail(g_heatbath_err, MCQ_EINVAL, "N = %d: the counter form of the heat-bath sweep runs N <= %d (MCQ_MAX_N_HEATBATH_COUNTERS); mcq_heatbath_device runs every N",
                              (int)q->N, MCQ_MAX_N_HEATBATH_COUNTERS);
     hipStream_t s = (hipStream_t)hip_stream;
     const HeatbathArgs a = heatbath_args(q);
@@ -566,7 +518,7 @@ int mcq_heatbath_counters_device(const mcq_heatbath* q, void* hip_stream) {
     else if (N <= 12) launch_heatbath_counters<12>(a, s);
     else launch_heatbath_counters<16>(a, s);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return heatbath_fail(MCQ_EDEVICE, "mcq_heatbath_counters_device: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(g_heatbath_err, MCQ_EDEVICE, "mcq_heatbath_counters_device: %s", hipGetErrorString(e));
     return MCQ_OK;
 }
 

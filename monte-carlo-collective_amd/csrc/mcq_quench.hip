@@ -21,23 +21,17 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
 #include <vector>
 
 #include "../../include/mcq.h"
+#include "mcq_post.h"
 
 namespace {
 
-thread_local char g_quench_err[256] = "";
+using mcq_post::fail;
+using mcq_post::host_counts;
 
-int quench_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_quench_err, sizeof g_quench_err, fmt, ap);
-    va_end(ap);
-    return code;
-}
+thread_local char g_quench_err[256] = "";
 
 struct QuenchArgs {
     const uint8_t* state_in;
@@ -146,22 +140,19 @@ __global__ __launch_bounds__(64) void mcq_quench_kernel(QuenchArgs a) {
     uint8_t* out = a.state_out + ch * Q;
     for (int c = lane; c < Q; c += GW) out[c] = h[c];
     if (lane == 0) {
-        if (a.energy_in) a.energy_in[ch] = e_in;
-        if (a.energy_out) a.energy_out[ch] = E;
-        if (a.n_moves) a.n_moves[ch] = moves;
-        if (a.n_passes) a.n_passes[ch] = passes;
+        mcq_post::store_quench_figures(a, ch, e_in, E, moves, passes);
     }
 }
 
 // what both entry points refuse
 int check_quench(const mcq_quench* q) {
-    if (!q) return quench_fail(MCQ_EINVAL, "mcq_quench: NULL parameter block");
-    if (q->mode != MCQ_MODE_BOARD) return quench_fail(MCQ_EINVAL, "mode: the quench runs boards only (MCQ_MODE_BOARD), got %d", (int)q->mode);
-    if (q->N < MCQ_MIN_N || q->N > MCQ_MAX_N_BOARD) return quench_fail(MCQ_EINVAL, "N out of range [%d, %d]: %d", MCQ_MIN_N, MCQ_MAX_N_BOARD, (int)q->N);
-    if (q->n_chains < 1 || q->n_chains > INT_MAX) return quench_fail(MCQ_EINVAL, "n_chains out of range [1, 2^31 - 1]: %lld", (long long)q->n_chains);
-    if (q->max_passes < 0) return quench_fail(MCQ_EINVAL, "max_passes must be >= 0 (0 = no limit), got %lld", (long long)q->max_passes);
-    if (!q->state_in) return quench_fail(MCQ_EINVAL, "state_in is required");
-    if (!q->state_out) return quench_fail(MCQ_EINVAL, "state_out is required");
+    if (!q) return fail(g_quench_err, MCQ_EINVAL, "mcq_quench: NULL parameter block");
+    if (q->mode != MCQ_MODE_BOARD) return fail(g_quench_err, MCQ_EINVAL, "mode: the quench runs boards only (MCQ_MODE_BOARD), got %d", (int)q->mode);
+    if (q->N < MCQ_MIN_N || q->N > MCQ_MAX_N_BOARD) return fail(g_quench_err, MCQ_EINVAL, "N out of range [%d, %d]: %d", MCQ_MIN_N, MCQ_MAX_N_BOARD, (int)q->N);
+    if (q->n_chains < 1 || q->n_chains > INT_MAX) return fail(g_quench_err, MCQ_EINVAL, "n_chains out of range [1, 2^31 - 1]: %lld", (long long)q->n_chains);
+    if (q->max_passes < 0) return fail(g_quench_err, MCQ_EINVAL, "max_passes must be >= 0 (0 = no limit), got %lld", (long long)q->max_passes);
+    if (!q->state_in) return fail(g_quench_err, MCQ_EINVAL, "state_in is required");
+    if (!q->state_out) return fail(g_quench_err, MCQ_EINVAL, "state_out is required");
     return MCQ_OK;
 }
 
@@ -169,25 +160,6 @@ template <int GW, int KPL, int NMAX>
 void launch_quench(const QuenchArgs& a, hipStream_t s) {
     constexpr int CPW = 64 / GW;
     hipLaunchKernelGGL((mcq_quench_kernel<GW, KPL, NMAX>), dim3((unsigned)((a.n_chains + CPW - 1) / CPW)), dim3(64), 0, s, a);
-}
-
-// a[k] = a(c, k) of column (i, j), k = 0 .. N - 1
-void host_counts(const uint8_t* h, int N, int i, int j, int* a) {
-    for (int k = 0; k < N; k++) a[k] = 0;
-    auto hit = [&](int hp, int d) {
-        a[hp]++;
-        if (hp - d >= 0) a[hp - d]++;
-        if (hp + d < N) a[hp + d]++;
-    };
-    for (int jj = 0; jj < N; jj++) {  // the row, and the two diagonal cells of board column jj
-        if (jj == j) continue;
-        const int d = jj > j ? jj - j : j - jj;
-        hit(h[i * N + jj], d);
-        if (i + d < N) hit(h[(i + d) * N + jj], d);
-        if (i - d >= 0) hit(h[(i - d) * N + jj], d);
-    }
-    for (int ii = 0; ii < N; ii++)  // the board column
-        if (ii != i) hit(h[ii * N + j], ii > i ? ii - i : i - ii);
 }
 
 }  // namespace
@@ -237,10 +209,7 @@ int mcq_quench_host(const mcq_quench* q) {
             }
         uint8_t* out = q->state_out + ch * Q;
         for (int c = 0; c < Q; c++) out[c] = h[(size_t)c];
-        if (q->energy_in) q->energy_in[ch] = e_in;
-        if (q->energy_out) q->energy_out[ch] = E;
-        if (q->n_moves) q->n_moves[ch] = moves;
-        if (q->n_passes) q->n_passes[ch] = passes;
+        mcq_post::store_quench_figures(*q, ch, e_in, E, moves, passes);
     }
     return MCQ_OK;
 }
@@ -256,7 +225,7 @@ int mcq_quench_device(const mcq_quench* q, void* hip_stream) {
     else if (q->N <= 64) launch_quench<64, 1, 64>(a, s);
     else launch_quench<64, 2, 128>(a, s);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return quench_fail(MCQ_EDEVICE, "mcq_quench_device: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(g_quench_err, MCQ_EDEVICE, "mcq_quench_device: %s", hipGetErrorString(e));
     return MCQ_OK;
 }
 

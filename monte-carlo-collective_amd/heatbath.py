@@ -14,7 +14,7 @@ reference, never a default.  anneal_heatbath runs either under a schedule (mcmc_
 import numpy as np
 
 from . import _lib, abi
-from .quench import _host_queens, _host_states, _queens_of
+from .quench import _device_out, _device_queens, _device_states, _host_outputs, _host_queens, _host_states, _queens_of
 
 FIELDS = ("state", "energy_in", "energy_out", "best_energy", "best_sweep", "best_state", "n_changed")
 FIELDS_3D = FIELDS + ("flags",)
@@ -48,26 +48,27 @@ def _host_seeds(seeds, n):
     return s
 
 
-def heatbath_states_host(N, states, seeds, betas, first_sweep=0, trace=False):
-    """mcq_heatbath_host: the rule in the library's plain host code, NumPy in and out, no GPU.  Same result as heatbath_states."""
-    s = _host_states(N, states)
+def _host_sweeps(block, run, s, seeds, betas, dtypes, trace):
+    """What the two *_host wrappers share: the seeds and the table checked, the parameter block from block(n_chains, n_sweeps, table),
+    _host_outputs with best_state next to state and the trace when asked for, and the call `run` of the library."""
     n = s.shape[0]
     seeds = _host_seeds(seeds, n)
     table = abi.heatbath_table(betas)
     n_sweeps = int(np.asarray(betas).size)
-    out = {"state": np.zeros_like(s), "best_state": np.zeros_like(s)}
-    for k, dt in abi.HEATBATH_DTYPES.items():
-        out[k] = np.zeros(n, dtype=dt)
-    q = _block(N, n, n_sweeps, first_sweep, table)
+    q = block(n, n_sweeps, table)
+    out = _host_outputs(q, s, dtypes, like=("best_state",))
     q.seeds, q.table = seeds.ctypes.data, table.ctypes.data
-    q.state_in, q.state_out, q.best_state = s.ctypes.data, out["state"].ctypes.data, out["best_state"].ctypes.data
-    for k in abi.HEATBATH_DTYPES:
-        setattr(q, k, out[k].ctypes.data)
     if trace:
         out["energy_hist"] = np.zeros((n, n_sweeps + 1), dtype=np.int32)
         q.energy_hist, q.hist_stride = out["energy_hist"].ctypes.data, n_sweeps + 1
-    _lib.heatbath_host(q)
+    run(q)
     return out
+
+
+def heatbath_states_host(N, states, seeds, betas, first_sweep=0, trace=False):
+    """mcq_heatbath_host: the rule in the library's plain host code, NumPy in and out, no GPU.  Same result as heatbath_states."""
+    return _host_sweeps(lambda n, n_sweeps, table: _block(N, n, n_sweeps, first_sweep, table), _lib.heatbath_host,
+                        _host_states(N, states), seeds, betas, abi.HEATBATH_DTYPES, trace)
 
 
 def _upload(a, dev):
@@ -103,11 +104,7 @@ def _device_buffers(states, seeds, betas, out, dtypes, trace, best_state):
             raise ValueError("seeds must be a contiguous int32 tensor [n_chains] on the device of states (the uint32 seeds bit for bit)")
     else:
         seeds = _upload(_host_seeds(seeds, n).view(np.int32), dev)
-    if out is None:
-        out = torch.empty_like(states)
-    elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-        raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
-    res = {"state": out}
+    res = {"state": _device_out(out, states)}
     tdt = {np.int32: torch.int32, np.int64: torch.int64}
     for k, dt in dtypes.items():
         res[k] = torch.empty(n, dtype=tdt[dt], device=dev)
@@ -140,11 +137,7 @@ def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=Fals
     _check_form(form, N)
     import torch
 
-    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
-        raise ValueError("heatbath_device takes a contiguous uint8 tensor on the GPU")
-    n = int(states.shape[0]) if states.dim() == 2 else 0
-    if states.dim() != 2 or (abi.MIN_N <= int(N) <= abi.MAX_N_BOARD and int(states.shape[1]) != int(N) * int(N)):
-        raise ValueError(f"states must be uint8[n_chains][{int(N) * int(N)}] (final_state layout of a board), got {tuple(states.shape)}")
+    n = _device_states("heatbath_device", N, states)
     dev = states.device
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.device(dev), torch.cuda.stream(st):
@@ -192,24 +185,8 @@ def _block3d(N, Q, n, n_sweeps, first_sweep, table):
 
 def heatbath_queens_host(N, states, seeds, betas, Q=None, first_sweep=0, trace=False):
     """mcq_heatbath3d_host: the full_3d rule in the library's plain host code, NumPy in and out, no GPU.  Same result as heatbath_queens."""
-    s = _host_queens(N, states, Q)
-    n, Qn = s.shape[0], _queens_of(N, Q)
-    seeds = _host_seeds(seeds, n)
-    table = abi.heatbath_table(betas)
-    n_sweeps = int(np.asarray(betas).size)
-    out = {"state": np.zeros_like(s), "best_state": np.zeros_like(s)}
-    for k, dt in abi.HEATBATH3D_DTYPES.items():
-        out[k] = np.zeros(n, dtype=dt)
-    q = _block3d(N, Qn, n, n_sweeps, first_sweep, table)
-    q.seeds, q.table = seeds.ctypes.data, table.ctypes.data
-    q.state_in, q.state_out, q.best_state = s.ctypes.data, out["state"].ctypes.data, out["best_state"].ctypes.data
-    for k in abi.HEATBATH3D_DTYPES:
-        setattr(q, k, out[k].ctypes.data)
-    if trace:
-        out["energy_hist"] = np.zeros((n, n_sweeps + 1), dtype=np.int32)
-        q.energy_hist, q.hist_stride = out["energy_hist"].ctypes.data, n_sweeps + 1
-    _lib.heatbath3d_host(q)
-    return out
+    return _host_sweeps(lambda n, n_sweeps, table: _block3d(N, _queens_of(N, Q), n, n_sweeps, first_sweep, table), _lib.heatbath3d_host,
+                        _host_queens(N, states, Q), seeds, betas, abi.HEATBATH3D_DTYPES, trace)
 
 
 def heatbath_queens_device(N, states, seeds, betas, Q=None, first_sweep=0, out=None, trace=False, best_state=True, stream=None):
@@ -221,13 +198,7 @@ def heatbath_queens_device(N, states, seeds, betas, Q=None, first_sweep=0, out=N
     best_state=False, and with trace=True `energy_hist` int32[n_chains][n_sweeps + 1]."""
     import torch
 
-    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
-        raise ValueError("heatbath_queens_device takes a contiguous uint8 tensor on the GPU")
-    Qn = _queens_of(N, Q)
-    ok = (states.dim() == 2 and int(states.shape[1]) == 3 * Qn) or (states.dim() == 3 and tuple(states.shape[1:]) == (Qn, 3))
-    if states.dim() not in (2, 3) or (abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and Qn >= 2 and not ok):
-        raise ValueError(f"states must be uint8[n_chains][{3 * Qn}] or [n_chains][{Qn}][3] (final_state layout of full_3d), got {tuple(states.shape)}")
-    n = int(states.shape[0])
+    n, Qn = _device_queens("heatbath_queens_device", N, states, Q)
     dev = states.device
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.device(dev), torch.cuda.stream(st):

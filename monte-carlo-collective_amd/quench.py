@@ -37,19 +37,82 @@ def _host_states(N, states):
     return s
 
 
+def _host_outputs(q, s, dtypes, shapes=None, skip=(), like=()):
+    """The host outputs of a call on the placements `s`, allocated from a *_DTYPES table -- one entry per chain, or the shape `shapes`
+    names; the fields in `skip` are left out -- with `state` and the uint8 arrays named in `like` shaped like s, and the block `q`
+    pointed at all of them and at s."""
+    out = {k: np.zeros_like(s) for k in ("state",) + tuple(like)}
+    for k, dt in dtypes.items():
+        if k not in skip:
+            out[k] = np.zeros((shapes or {}).get(k, s.shape[0]), dtype=dt)
+    q.state_in, q.state_out = s.ctypes.data, out["state"].ctypes.data
+    for k in tuple(like) + tuple(dtypes):
+        if k in out:
+            setattr(q, k, out[k].ctypes.data)
+    return out
+
+
+def _device_tensor(fn, states):
+    """ValueError unless `states` is what the wrapper `fn` takes: a contiguous uint8 tensor on the GPU."""
+    import torch
+
+    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
+        raise ValueError(f"{fn} takes a contiguous uint8 tensor on the GPU")
+
+
+def _device_states(fn, N, states):
+    """The checks of a device tensor of boards, [n_chains][N*N]; returns n_chains."""
+    _device_tensor(fn, states)
+    n = int(states.shape[0]) if states.dim() == 2 else 0
+    if states.dim() != 2 or (abi.MIN_N <= int(N) <= abi.MAX_N_BOARD and int(states.shape[1]) != int(N) * int(N)):
+        raise ValueError(f"states must be uint8[n_chains][{int(N) * int(N)}] (final_state layout of a board), got {tuple(states.shape)}")
+    return n
+
+
+def _device_queens(fn, N, states, Q):
+    """The checks of a device tensor of full_3d placements, [n_chains][3 Q] or [n_chains][Q][3]; returns (n_chains, Q)."""
+    _device_tensor(fn, states)
+    Qn = _queens_of(N, Q)
+    ok = (states.dim() == 2 and int(states.shape[1]) == 3 * Qn) or (states.dim() == 3 and tuple(states.shape[1:]) == (Qn, 3))
+    if states.dim() not in (2, 3) or (abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and Qn >= 2 and not ok):
+        raise ValueError(f"states must be uint8[n_chains][{3 * Qn}] or [n_chains][{Qn}][3] (final_state layout of full_3d), got {tuple(states.shape)}")
+    return int(states.shape[0]), Qn
+
+
+def _device_out(out, states):
+    """The tensor the placements go to: `out` when given (checked; it may be `states`), a new one otherwise."""
+    import torch
+
+    if out is None:
+        return torch.empty_like(states)
+    if out.shape != states.shape or out.dtype != torch.uint8 or out.device != states.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
+    return out
+
+
+def _device_outputs(q, states, out, dtypes, conflicts):
+    """The result tensors of a quench on the device, from a *_DTYPES table -- int32 per chain, and `conflicts` int16 of the shape given
+    (None: left out) --, with the block `q` pointed at them and at `states`.  `out` is _device_out's."""
+    import torch
+
+    res = {"state": _device_out(out, states)}
+    for k in dtypes:
+        if k != "conflicts":
+            res[k] = torch.empty(int(states.shape[0]), dtype=torch.int32, device=states.device)
+        elif conflicts is not None:
+            res[k] = torch.empty(conflicts, dtype=torch.int16, device=states.device)
+    q.state_in, q.state_out = states.data_ptr(), res["state"].data_ptr()
+    for k in dtypes:
+        if k in res:
+            setattr(q, k, res[k].data_ptr())
+    return res
+
+
 def quench_states_host(N, states, max_passes=0, conflicts=True):
     """mcq_quench_host: the rule in the library's plain host code, NumPy in and out, no GPU.  Same result as quench_states."""
     s = _host_states(N, states)
-    n = s.shape[0]
-    out = {"state": np.zeros_like(s)}
-    for k, dt in abi.QUENCH_DTYPES.items():
-        if k != "conflicts" or conflicts:
-            out[k] = np.zeros((n, s.shape[1]) if k == "conflicts" else n, dtype=dt)
-    q = _block(N, n, max_passes)
-    q.state_in, q.state_out = s.ctypes.data, out["state"].ctypes.data
-    for k in abi.QUENCH_DTYPES:
-        if k in out:
-            setattr(q, k, out[k].ctypes.data)
+    q = _block(N, s.shape[0], max_passes)
+    out = _host_outputs(q, s, abi.QUENCH_DTYPES, {"conflicts": s.shape}, () if conflicts else ("conflicts",))
     _lib.quench_host(q)
     return out
 
@@ -63,28 +126,12 @@ def quench_device(N, states, max_passes=0, out=None, conflicts=True, stream=None
     output; at most 4 (N - 1), so the sign bit is never set)."""
     import torch
 
-    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
-        raise ValueError("quench_device takes a contiguous uint8 tensor on the GPU")
-    n = int(states.shape[0]) if states.dim() == 2 else 0
-    if states.dim() != 2 or (abi.MIN_N <= int(N) <= abi.MAX_N_BOARD and int(states.shape[1]) != int(N) * int(N)):
-        raise ValueError(f"states must be uint8[n_chains][{int(N) * int(N)}] (final_state layout of a board), got {tuple(states.shape)}")
+    n = _device_states("quench_device", N, states)
     dev = states.device
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.device(dev), torch.cuda.stream(st):
-        if out is None:
-            out = torch.empty_like(states)
-        elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
-        res = {"state": out}
-        for k in ("energy_in", "energy_out", "n_moves", "n_passes"):
-            res[k] = torch.empty(n, dtype=torch.int32, device=dev)
-        if conflicts:
-            res["conflicts"] = torch.empty(tuple(states.shape), dtype=torch.int16, device=dev)
         q = _block(N, n, max_passes)
-        q.state_in, q.state_out = states.data_ptr(), out.data_ptr()
-        for k in abi.QUENCH_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
+        res = _device_outputs(q, states, out, abi.QUENCH_DTYPES, tuple(states.shape) if conflicts else None)
         _lib.quench_device(q, st)
     return res
 
@@ -145,16 +192,9 @@ def _host_queens(N, states, Q):
 def quench_queens_host(N, states, Q=None, max_passes=0, conflicts=True):
     """mcq_quench3d_host: the full_3d rule in the library's plain host code, NumPy in and out, no GPU.  Same result as quench_queens."""
     s = _host_queens(N, states, Q)
-    n, Qn = s.shape[0], _queens_of(N, Q)
-    out = {"state": np.zeros_like(s)}
-    for k, dt in abi.QUENCH3D_DTYPES.items():
-        if k != "conflicts" or conflicts:
-            out[k] = np.zeros((n, s.shape[1] // 3) if k == "conflicts" else n, dtype=dt)
-    q = _block3d(N, Qn, n, max_passes)
-    q.state_in, q.state_out = s.ctypes.data, out["state"].ctypes.data
-    for k in abi.QUENCH3D_DTYPES:
-        if k in out:
-            setattr(q, k, out[k].ctypes.data)
+    n = s.shape[0]
+    q = _block3d(N, _queens_of(N, Q), n, max_passes)
+    out = _host_outputs(q, s, abi.QUENCH3D_DTYPES, {"conflicts": (n, s.shape[1] // 3)}, () if conflicts else ("conflicts",))
     _lib.quench3d_host(q)
     return out
 
@@ -168,30 +208,12 @@ def quench_queens_device(N, states, Q=None, max_passes=0, out=None, conflicts=Tr
     `conflicts` int16[n_chains][Q] (the uint16 counts a(q, pos(q)) of the output; below 2^15, so the sign bit is never set)."""
     import torch
 
-    if not (isinstance(states, torch.Tensor) and states.is_cuda and states.dtype == torch.uint8 and states.is_contiguous()):
-        raise ValueError("quench_queens_device takes a contiguous uint8 tensor on the GPU")
-    Qn = _queens_of(N, Q)
-    ok = (states.dim() == 2 and int(states.shape[1]) == 3 * Qn) or (states.dim() == 3 and tuple(states.shape[1:]) == (Qn, 3))
-    if states.dim() not in (2, 3) or (abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and Qn >= 2 and not ok):
-        raise ValueError(f"states must be uint8[n_chains][{3 * Qn}] or [n_chains][{Qn}][3] (final_state layout of full_3d), got {tuple(states.shape)}")
-    n = int(states.shape[0])
+    n, Qn = _device_queens("quench_queens_device", N, states, Q)
     dev = states.device
     st = torch.cuda.current_stream(dev) if stream is None else stream
     with torch.cuda.device(dev), torch.cuda.stream(st):
-        if out is None:
-            out = torch.empty_like(states)
-        elif out.shape != states.shape or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 tensor of the shape and device of states")
-        res = {"state": out}
-        for k in ("energy_in", "energy_out", "n_moves", "n_passes", "flags"):
-            res[k] = torch.empty(n, dtype=torch.int32, device=dev)
-        if conflicts:
-            res["conflicts"] = torch.empty((n, Qn), dtype=torch.int16, device=dev)
         q = _block3d(N, Qn, n, max_passes)
-        q.state_in, q.state_out = states.data_ptr(), out.data_ptr()
-        for k in abi.QUENCH3D_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
+        res = _device_outputs(q, states, out, abi.QUENCH3D_DTYPES, (n, Qn) if conflicts else None)
         _lib.quench3d_device(q, st)
     return res
 
