@@ -491,12 +491,15 @@ int mcq_quench_host(const mcq_quench* q);
  *   3. for column c: a_min = min_k a(c, k); w_k = T_s[min(a(c, k) - a_min, D - 1)], T_s = the caller's row for sweep s (uint32,
  *      D = table_len entries, 1 <= D <= MCQ_MAX_HEATBATH_TABLE); C_k = w_0 + .. + w_k in uint32 (k = 0 .. N - 1), W = C_{N-1}.
  *      The Python side builds T_s[d] = floor(2^24 exp(-beta_s d)) in float64 with NumPy, beta_s >= 0, so T_s[0] = 2^24 and
- *      W <= 128 * 2^24 = 2^31; D = 1 + the first d with T = 0 over the call's rows, at most 512, rows zero-padded.
+ *      W <= 128 * 2^24 = 2^31; D = 1 + the first d with T = 0 over the call's rows, at most 512, rows zero-padded.  A caller's own
+ *      table is as good, and every entry of T is at most 2^MCQ_HEATBATH_WEIGHT_BITS = 2^24: W then stays below 2^32 at N = 128, so
+ *      the uint32 sums do not wrap and C is non-decreasing.
  *   4. one 32-bit word x per (chain, sweep, column): word w = g N^2 + c (64-bit) of chain r is
  *      philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[r], 1))[w % 4] -- the definition of
  *      MCQ_RNG_PHILOX4X32_10 with key word 1 instead of 0, so the two streams are independent.  The state of a chain is its placement
  *      plus a sweep index, and nothing else.
- *   5. U = floor(x W / 2^32) from the full 64-bit product; the new height is the smallest k with C_k > U.
+ *   5. U = floor(x W / 2^32) from the full 64-bit product; the new height is the smallest k with C_k > U.  W = 0 (only a table with
+ *      T[0] = 0 gives it) has no such k: the column takes the height N - 1.
  *      E += a(c, k_new) - a(c, k_old); n_changed counts the updates with k_new != k_old.
  *   6. best values are taken at sweep ends only: initially best_energy = the recount of the clamped input, best_sweep = 0 and
  *      best_state = the clamped input; after sweep s a STRICTLY lower E sets best_energy, best_sweep = s + 1 (relative to the call)
@@ -536,12 +539,15 @@ const char* mcq_heatbath_last_error(void);
  * synchronises.  MCQ_EINVAL before any launch: mode other than board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative
  * n_sweeps or first_sweep, (first_sweep + n_sweeps) N^2 >= 2^63, table_len outside 1 .. 512, a NULL seeds, state_in or state_out, a NULL
  * table with n_sweeps > 0, hist_stride < n_sweeps + 1 with energy_hist given.  NOT checked, being on the device: a table with
- * T[0] = 0 can give W = 0, and the column then takes the height N - 1; nothing leaves the arrays. */
+ * T[0] = 0 can give W = 0, and the column then takes the height N - 1; nothing leaves the arrays.  An entry of T above
+ * 2^MCQ_HEATBATH_WEIGHT_BITS (rule item 3) is not checked either: the sums may wrap, and the outputs are then no longer the rule's. */
 int mcq_heatbath_device(const mcq_heatbath* q, void* hip_stream);
-/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output.
+ * It reads the table, so it also refuses an entry above 2^MCQ_HEATBATH_WEIGHT_BITS with MCQ_EINVAL; the message names the sweep, the
+ * index and the value. */
 int mcq_heatbath_host(const mcq_heatbath* q);
-/* The counter form of the same sweep for N <= MCQ_MAX_N_HEATBATH_COUNTERS: the same parameter block, the same refusals and the same
- * asynchrony as mcq_heatbath_device, and MCQ_EINVAL before any launch for a larger N (mcq_heatbath_device runs every N).  Its outputs
+/* The counter form of the same sweep for N <= MCQ_MAX_N_HEATBATH_COUNTERS: the same parameter block, the same refusals, the same
+ * asynchrony and the same two things NOT checked (T[0] = 0, an entry above 2^MCQ_HEATBATH_WEIGHT_BITS) as mcq_heatbath_device, and MCQ_EINVAL before any launch for a larger N (mcq_heatbath_device runs every N).  Its outputs
  * equal those of mcq_heatbath_device and of mcq_heatbath_host bit for bit: the rule above is one rule, and only the way a(c, k) is
  * obtained differs.  Take the 12 line families of the cube with in-plane direction (0,1), (1,0), (1,1), (1,-1) and height step 0, +1,
  * -1 per cell, and let cnt_f(l) be the number of queens of the (clamped) board on line l of family f (at most N, a byte).  Then for a
@@ -626,7 +632,9 @@ int mcq_quench3d_host(const mcq_quench3d* q);
  *      of the cell index t = i N^2 + j N + k.  a_min = the smallest a(q, t) over the candidates; w_t = T_s[min(a(q, t) - a_min, D - 1)]
  *      for a candidate and 0 for an occupied cell, T_s = the caller's row for sweep s (uint32, D = table_len entries,
  *      1 <= D <= MCQ_MAX_HEATBATH_TABLE; the rows of the board heat-bath, T[d] = floor(2^24 exp(-beta_s d)); a <= 403 < 512).
- *      C_t = w_0 + .. + w_t over ALL cells in index order, in uint64; W = C_{N^3 - 1} <= 2^15 2^24 = 2^39.
+ *      C_t = w_0 + .. + w_t over ALL cells in index order, in uint64; W = C_{N^3 - 1} <= 2^15 2^24 = 2^39.  Every entry of T is at
+ *      most 2^MCQ_HEATBATH_WEIGHT_BITS = 2^24, in a caller's own table too: the kernel adds up to 34 consecutive w_t in 32 bits before
+ *      it goes to 64, and 34 * 2^24 < 2^30.
  *   4. two 32-bit words per (chain, sweep, queen): with u = g Q + q (64-bit) they are the words 2 u and 2 u + 1 of the stream
  *      word w = philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[r], 2))[w % 4] -- key word 0 is
  *      MCQ_RNG_PHILOX4X32_10 of the sweep and 1 the board heat-bath, so the three streams are independent.  Both words lie in block
@@ -674,9 +682,12 @@ const char* mcq_heatbath3d_last_error(void);
  * synchronises.  MCQ_EINVAL before any launch: a NULL block, seeds, state_in or state_out, a NULL table with n_sweeps > 0, N outside
  * 2 .. 32 (33 .. 64 named as this build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, a negative
  * n_sweeps or first_sweep, (first_sweep + n_sweeps) Q >= 2^62, table_len outside 1 .. 512, hist_stride < n_sweeps + 1 with
- * energy_hist given. */
+ * energy_hist given.  NOT checked, being on the device: a table with T[0] = 0 can give W = 0, and the queen then stays where it is; an
+ * entry of T above 2^MCQ_HEATBATH_WEIGHT_BITS (rule item 3) can wrap a 32-bit partial sum, and the outputs are then no longer the rule's. */
 int mcq_heatbath3d_device(const mcq_heatbath3d* q, void* hip_stream);
-/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output.
+ * It reads the table, so it also refuses an entry above 2^MCQ_HEATBATH_WEIGHT_BITS with MCQ_EINVAL; the message names the sweep, the
+ * index and the value. */
 int mcq_heatbath3d_host(const mcq_heatbath3d* q);
 
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */

@@ -227,7 +227,8 @@ HEATBATH_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "best_energy":
 def heatbath_table(betas):
     """The weight rows of a heat-bath call (include/mcq.h, heat-bath rule, step 3): T[s][d] = floor(2^24 exp(-beta_s d)) as uint32 for
     d = 0 .. D - 1, one row per sweep; D = 1 + the first d with T = 0 over the rows, at most 512, the rows zero-padded.  NumPy's exp /
-    floor on float64.  No sweep gives one row [2^24] that no sweep reads."""
+    floor on float64.  No sweep gives one row [2^24] that no sweep reads.  No entry exceeds 2^HEATBATH_WEIGHT_BITS, the bound the rule
+    sets for every table, a caller's own included (the host entry points refuse a larger entry; the device ones cannot look)."""
     b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
     if not (np.isfinite(b).all() and (b >= 0.0).all()):
         raise ValueError("the heat-bath sweep needs finite beta >= 0 for every sweep")

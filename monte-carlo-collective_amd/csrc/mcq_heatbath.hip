@@ -402,6 +402,17 @@ int check_heatbath(const mcq_heatbath* q) {
     return MCQ_OK;
 }
 
+// what the host entry point refuses on top of that: it reads the table, which the device entry points cannot
+int check_heatbath_table(const mcq_heatbath* q) {
+    const long long D = (long long)q->table_len;
+    for (long long s = 0; s < q->n_sweeps; s++)
+        for (long long d = 0; d < D; d++)
+            if (q->table[s * D + d] > (1u << MCQ_HEATBATH_WEIGHT_BITS))
+                return fail(g_heatbath_err, MCQ_EINVAL, "table: the entry of sweep %lld at index %lld is %u, above 2^%d (W must stay below 2^32 at N = 128)",
+                            s, d, (unsigned)q->table[s * D + d], MCQ_HEATBATH_WEIGHT_BITS);
+    return MCQ_OK;
+}
+
 template <int GW, int KPL, int NP>
 void launch_heatbath(const HeatbathArgs& a, hipStream_t s) {
     constexpr int CPW = 64 / GW;
@@ -426,7 +437,8 @@ extern "C" {
 const char* mcq_heatbath_last_error(void) { return g_heatbath_err; }
 
 int mcq_heatbath_host(const mcq_heatbath* q) {
-    const int rc = check_heatbath(q);
+    int rc = check_heatbath(q);
+    if (rc == MCQ_OK) rc = check_heatbath_table(q);
     if (rc != MCQ_OK) return rc;
     const int N = q->N, Q = N * N, D = (int)q->table_len;
     std::vector<uint8_t> h((size_t)Q);

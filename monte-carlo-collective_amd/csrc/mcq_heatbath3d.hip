@@ -16,7 +16,7 @@
 //             2. the weights.  Cell-index order is part of the rule, so lane l owns the CONTIGUOUS run of R field dwords from l R on,
 //                R = ceil(dwords / W) rounded up to an ODD number: ds_read_b32 banks by dword index mod 32 over each half of the
 //                wavefront, and an odd stride sends the 32 lanes of a half to 32 different banks.  R <= 17 dwords = 34 cells at N = 32
-//                and 7 dwords = 28 cells at N <= 19, so a lane's own sum stays below 2^30; the prefix over lanes is 64-bit: DPP row
+//                and 7 dwords = 28 cells at N <= 19, so with entries of at most 2^24 (the rule, item 3) a lane's own sum stays below 2^30; the prefix over lanes is 64-bit: DPP row
 //                shifts inside a row of 16 lanes, the four row totals by v_readlane, the wavefront totals through `scan`;
 //             3. U = __umul64hi(x, W), and the ONE lane whose interval [P, P + sum) holds U walks its run again and writes the winner
 //                to `win`.  Everything after that barrier is uniform over the workgroup, so every barrier is reached by all lanes;
@@ -273,6 +273,17 @@ int check_heatbath3d(const mcq_heatbath3d* q) {
     return MCQ_OK;
 }
 
+// what the host entry point refuses on top of that: it reads the table, which the device entry point cannot
+int check_heatbath3d_table(const mcq_heatbath3d* q) {
+    const long long D = (long long)q->table_len;
+    for (long long s = 0; s < q->n_sweeps; s++)
+        for (long long d = 0; d < D; d++)
+            if (q->table[s * D + d] > (1u << MCQ_HEATBATH_WEIGHT_BITS))
+                return fail(g_heatbath3d_err, MCQ_EINVAL, "table: the entry of sweep %lld at index %lld is %u, above 2^%d (a lane sums up to 34 entries in 32 bits)",
+                            s, d, (unsigned)q->table[s * D + d], MCQ_HEATBATH_WEIGHT_BITS);
+    return MCQ_OK;
+}
+
 // chains first .. last - 1 through the rule, with an int field per cell
 void host_chains(const mcq_heatbath3d* q, long long first, long long last) {
     const int Q = queens_of(q), D = (int)q->table_len;
@@ -348,7 +359,8 @@ extern "C" {
 const char* mcq_heatbath3d_last_error(void) { return g_heatbath3d_err; }
 
 int mcq_heatbath3d_host(const mcq_heatbath3d* q) {
-    const int rc = check_heatbath3d(q);
+    int rc = check_heatbath3d(q);
+    if (rc == MCQ_OK) rc = check_heatbath3d_table(q);
     if (rc != MCQ_OK) return rc;
     mcq_post::for_chains(q->n_chains, [q](long long first, long long last) { host_chains(q, first, last); });
     return MCQ_OK;

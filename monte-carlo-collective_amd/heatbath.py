@@ -81,7 +81,9 @@ def _upload(a, dev):
 def device_table(betas, device):
     """abi.heatbath_table(betas) on the device as an int32 tensor [n_sweeps][table_len] (the uint32 weights bit for bit), uploaded on
     torch's current stream: what heatbath_device takes in place of `betas`, whole or as a slice of rows (a slice of a longer run's table
-    is as good as the slice's own: a row is zero from its first zero on, so a larger table_len reads the same weights)."""
+    is as good as the slice's own: a row is zero from its first zero on, so a larger table_len reads the same weights).  A caller may
+    pass a tensor of its own weights in that place; every entry must then be at most 2^abi.HEATBATH_WEIGHT_BITS = 2^24 as uint32
+    (include/mcq.h, item 3 of either rule), which nothing on the device path checks."""
     return _upload(abi.heatbath_table(betas).view(np.int32), device)
 
 
@@ -133,7 +135,9 @@ def heatbath_device(N, states, seeds, betas, first_sweep=0, out=None, trace=Fals
     Returns a dict of tensors: `state`, `energy_in` (the recount of the input), `energy_out`, `best_energy` int32[n_chains],
     `best_sweep`, `n_changed` int64[n_chains], `best_state` unless best_state=False, and with trace=True `energy_hist`
     int32[n_chains][n_sweeps + 1].  `form` is one of FORMS: "counters" runs mcq_heatbath_counters_device (N <= 16; the same results bit
-    for bit); an unknown form, or "counters" with a larger N, is a ValueError before anything else is looked at."""
+    for bit); an unknown form, or "counters" with a larger N, is a ValueError before anything else is looked at.
+    A `betas` tensor of the caller's own weights must hold no entry above 2^24 (read as uint32): beyond it the kernels' 32-bit sums can
+    wrap (W < 2^32 at N = 128 needs it).  It is NOT checked here: a check would read the tensor back and synchronise."""
     _check_form(form, N)
     import torch
 
@@ -195,7 +199,9 @@ def heatbath_queens_device(N, states, seeds, betas, Q=None, first_sweep=0, out=N
     nothing synchronises.  `seeds`, `betas` and `out` are those of heatbath_device: tensors already on the device or host values that are
     uploaded on the stream; `out` may be `states` itself (in place).  Returns a dict of tensors: `state` like `states`, `energy_in`,
     `energy_out`, `best_energy`, `flags` int32[n_chains], `best_sweep`, `n_changed` int64[n_chains], `best_state` unless
-    best_state=False, and with trace=True `energy_hist` int32[n_chains][n_sweeps + 1]."""
+    best_state=False, and with trace=True `energy_hist` int32[n_chains][n_sweeps + 1].
+    A `betas` tensor of the caller's own weights must hold no entry above 2^24 (read as uint32): a lane of the kernel sums up to 34
+    entries in 32 bits.  It is NOT checked here: a check would read the tensor back and synchronise."""
     import torch
 
     n, Qn = _device_queens("heatbath_queens_device", N, states, Q)

@@ -64,7 +64,7 @@ def sweeps(N, board, seed, tab, n_sweeps, first_sweep=0):
             W = C[-1]
             x = word(seed, g * Q + c)
             U = (x * W) >> 32
-            k_new = next(k for k in range(N) if C[k] > U)
+            k_new = next((k for k in range(N) if C[k] > U), N - 1)  # (W = 0, a table with T[0] = 0: no such k, the height N - 1)
             words.append((x, U, W))
             E += a[k_new] - a[int(h[c])]
             changed += k_new != int(h[c])

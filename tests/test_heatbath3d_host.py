@@ -13,28 +13,11 @@ import mcq_amd
 from tests import heatbath3d_util as h3
 from tests import heatbath_util as hu
 from tests import quench3d_util as q3
+from tests.heatbath_tables_util import host3d as _raw
 
 abi = mcq_amd.abi
 heatbath = mcq_amd.heatbath
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _raw(N, Q, states, seeds, table, n_sweeps, first_sweep=0, fn=None):
-    """mcq_heatbath3d_host on a caller's table (heatbath_queens_host builds its own from betas)."""
-    s = np.ascontiguousarray(states, dtype=np.uint8).reshape(len(seeds), 3 * Q)
-    n = len(s)
-    sd, tab = np.ascontiguousarray(seeds, dtype=np.uint32), np.ascontiguousarray(table, dtype=np.uint32)
-    out = {"state": np.zeros_like(s), "best_state": np.zeros_like(s), "energy_hist": np.zeros((n, n_sweeps + 1), dtype=np.int32)}
-    for k, dt in abi.HEATBATH3D_DTYPES.items():
-        out[k] = np.zeros(n, dtype=dt)
-    q = abi.Heatbath3D()
-    q.N, q.n_queens, q.n_chains, q.n_sweeps, q.first_sweep, q.table_len = N, Q, n, n_sweeps, first_sweep, tab.shape[1]
-    q.seeds, q.table, q.state_in, q.hist_stride = sd.ctypes.data, tab.ctypes.data, s.ctypes.data, n_sweeps + 1
-    q.state_out = out["state"].ctypes.data
-    for k in tuple(abi.HEATBATH3D_DTYPES) + ("best_state", "energy_hist"):
-        setattr(q, k, out[k].ctypes.data)
-    mcq_amd._lib.heatbath3d_host(q)
-    return out
 
 
 def test_philox_words_with_key_word_two_are_the_oracles():

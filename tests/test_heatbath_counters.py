@@ -15,6 +15,7 @@ from tests import heatbath_counters_util as cu
 from tests import heatbath_util as hu
 from tests import population_util as pu
 from tests import quench_util as qu
+from tests.heatbath_tables_util import host_with_table as _host_with_table
 
 abi = mcq_amd.abi
 heatbath = mcq_amd.heatbath
@@ -44,25 +45,6 @@ def _seeds(n, k):
     s = (np.arange(n, dtype=np.uint64) * 2654435761 + k) % 2**32
     s[-1] = 2**32 - 1
     return s.astype(np.uint32)
-
-
-def _host_with_table(N, s, seeds, tab, first_sweep, trace):
-    """mcq_heatbath_host with the caller's own weight table uint32[n_sweeps][D]."""
-    n, n_sweeps = s.shape[0], tab.shape[0]
-    out = {"state": np.zeros_like(s), "best_state": np.zeros_like(s)}
-    for k, dt in abi.HEATBATH_DTYPES.items():
-        out[k] = np.zeros(n, dtype=dt)
-    q = abi.Heatbath()
-    q.N, q.mode, q.n_chains, q.n_sweeps, q.first_sweep, q.table_len = N, abi.MODE_BOARD, n, n_sweeps, first_sweep, tab.shape[1]
-    q.seeds, q.table = seeds.ctypes.data, tab.ctypes.data
-    q.state_in, q.state_out, q.best_state = s.ctypes.data, out["state"].ctypes.data, out["best_state"].ctypes.data
-    for k in abi.HEATBATH_DTYPES:
-        setattr(q, k, out[k].ctypes.data)
-    if trace:
-        out["energy_hist"] = np.zeros((n, n_sweeps + 1), dtype=np.int32)
-        q.energy_hist, q.hist_stride = out["energy_hist"].ctypes.data, n_sweeps + 1
-    mcq_amd._lib.heatbath_host(q)
-    return out
 
 
 @pytest.mark.parametrize("N", range(2, 17))
