@@ -2,7 +2,7 @@
 
 A Checkpoint holds what defines a run (N, chain type, Q, the schedule(s) and the length of the WHOLE schedule, the seeds, the trace
 mode), how many steps are done, and per chain the placement, the MT19937 state as np.random.get_state() holds it, the energy, and the
-running summary of the whole run so far (best energy / state / step, accepted steps, words taken from the stream).  The segments come
+running summary of the whole run so far (best energy / state / step, accepted steps, near ties, words taken from the stream).  The segments come
 from the GPU (experiments.start_chains / continue_chains / warm_start_chains); merging them is plain NumPy and lives here.
 
 The merge rules follow from what the reference reports for one unbroken chain (experiments.py:329-365): best_energy is
@@ -15,7 +15,7 @@ import numpy as np
 from . import abi
 
 FORMAT = 1
-_PER_CHAIN = ("state", "stream_state", "energy", "best_energy", "best_state", "steps_to_best", "n_accepted", "stream_words")
+_PER_CHAIN = ("state", "stream_state", "energy", "best_energy", "best_state", "steps_to_best", "n_accepted", "stream_words", "near_ties")
 
 
 class Checkpoint:
@@ -60,8 +60,8 @@ class Checkpoint:
 
     def merge(self, seg, seg_steps):
         """Take in the result of the segment that ran steps [self.step, self.step + seg_steps): a dict with initial_energy, final_energy,
-        best_energy, steps_to_best and n_accepted per chain and, where the segment has them, best_state, final_state, stream_state and
-        stream_words.  Raises ValueError when the segment did not start where the checkpoint stands."""
+        best_energy, steps_to_best and n_accepted per chain and, where the segment has them, best_state, final_state, stream_state,
+        stream_words and near_ties (which add up, like n_accepted).  Raises ValueError when the segment did not start where the checkpoint stands."""
         seg_steps = int(seg_steps)
         if seg_steps < 0 or self.step + seg_steps > self.schedule_steps:
             raise ValueError(f"a segment of {seg_steps} steps from step {self.step} leaves the schedule of {self.schedule_steps} steps")
@@ -73,6 +73,8 @@ class Checkpoint:
             self.best_energy, self.steps_to_best = sbest.copy(), sstb + self.step
             self.n_accepted = np.asarray(seg["n_accepted"]).astype(np.int64).copy()
             self.stream_words = np.zeros(self.n_chains, dtype=np.uint64)
+            if seg.get("near_ties") is not None:  # counted from the first segment on, or not at all
+                self.near_ties = np.asarray(seg["near_ties"]).astype(np.int64).copy()
             if seg.get("best_state") is not None:
                 self.best_state = np.array(seg["best_state"], dtype=np.uint8)
         else:
@@ -85,6 +87,9 @@ class Checkpoint:
             if seg.get("best_state") is not None and self.best_state is not None:
                 self.best_state = np.where(lower[:, None], np.asarray(seg["best_state"], dtype=np.uint8), self.best_state)
             self.n_accepted = self.n_accepted + np.asarray(seg["n_accepted"]).astype(np.int64)
+            # a checkpoint without the count (saved by an earlier version, or a segment that lacked it) stays without: a sum of the later
+            # segments alone would pass for the run's
+            self.near_ties = None if self.near_ties is None or seg.get("near_ties") is None else self.near_ties + np.asarray(seg["near_ties"]).astype(np.int64)
         if seg.get("stream_words") is not None:
             self.stream_words = self.stream_words + np.asarray(seg["stream_words"]).astype(np.uint64)
         self.energy = np.asarray(seg["final_energy"]).astype(np.int64).copy()

@@ -1,0 +1,325 @@
+"""Crafting of beta tables that put a chain's uniform next to its acceptance probability (tests/test_near_ties_host.py, tests/test_near_ties.py).
+
+A caller's mcq_params.beta_table is followed exactly, the proposal of step s does not depend on beta(s), and the uniform of a step is always
+drawn and is the last two words of the step.  So for a chosen (step s, chain c) the CPU oracle, run for s + 1 steps under the table as
+crafted so far with beta(s) = 0 (everything is accepted), tells dE = energy_hist[s + 1] - energy_hist[s] and, through stream_words, the two
+words of u = ((w1 >> 5) 2^26 + (w2 >> 6)) 2^-53.  With dE > 0 and x = -ln(u) in [0.05, 1], beta(s) is then walked through the float64
+neighbours of x / dE until math.exp(-beta dE) -- glibc's exp, the oracle's -- stands at the wanted SIGNED distance from u; x <= 1 makes one
+ulp of beta move exp by less than one ulp, so every distance is hit.  A step that does not qualify hands over to the next step of the chain.
+Points are placed in step order: each is derived under the table all earlier points have already changed.
+
+Nothing here touches a GPU, and nothing looks at a result of the code under test: the expected counts are the crafted ones.
+
+Kinds of points (signed distance d = position of the probability minus position of u, so d > 0 accepts):
+  count    d = +-2, +-3 ulp: a near tie (|d| <= 4) that stays one, and keeps its decision, while the device's exp and glibc's agree within 1 ulp
+  miss     d = +-8 ulp: no tie
+  bracket  probability = u (1 + delta) with |delta| from 2^-40 up to 2^-9: inside, at the edge of, and outside the float32 bracket
+           (half-width e27 2^-10 + 1/2); never a tie
+  behind   (early-stop cases) a +2 ulp tie of a chain at a step behind the one it stopped at: never executed, so it must not count
+Distances 0, +-1 and +-4 .. +-7 are left out: there the two exp may legitimately disagree about the count or the decision.
+"""
+import math
+import struct
+
+import numpy as np
+
+import mcq_amd
+from oracle import oracle
+
+abi = mcq_amd.abi
+
+SET_CHAINS = 16  # chains_per_set is a multiple of 16: one table row serves 16 chains (one wavefront at 4 lanes per chain)
+SET_CHAINS_2 = 32  # ... and of 32 at 2 lanes per chain, where a wavefront holds 32 chains and belongs to one set
+COUNT_ULPS = (2, -2, 3, -3)
+MISS_ULPS = (8, -8)
+# (2^-17 .. 2^-22: around the error of the float32 estimate of exp, where a bracket narrower than that error decides wrongly)
+BRACKET_DELTAS = tuple(s * m for m in (2.0 ** -40, 2.0 ** -30, 2.0 ** -22, 2.0 ** -21, 2.0 ** -20, 2.0 ** -19, 2.0 ** -18, 2.0 ** -17, 2.0 ** -16, 2.0 ** -14,
+                                       2.0 ** -12, 0.9 * 2.0 ** -10, 1.1 * 2.0 ** -10, 2.0 ** -9) for s in (1.0, -1.0))
+X_MIN, X_MAX = 0.05, 1.0
+WALK = 400
+
+
+def _bits(x):
+    return struct.unpack("<q", struct.pack("<d", x))[0]
+
+
+def _from_bits(b):
+    return struct.unpack("<d", struct.pack("<q", b))[0]
+
+
+def signed_ulps(prob, u):
+    """Position of `prob` minus position of `u` among the float64 values (both positive and finite)."""
+    return _bits(prob) - _bits(u)
+
+
+def uniform_of(w1, w2):
+    """NumPy's random_sample from two 32-bit words: 53 bits, exact in float64."""
+    return ((int(w1) >> 5) * 67108864 + (int(w2) >> 6)) / 9007199254740992.0
+
+
+class Case:
+    """One launch: n_sets sets of 16 chains (32 at 2 lanes per chain), each under its own table row."""
+
+    def __init__(self, name, mode, N, lanes, n_sets=4, n_steps=330, trace=True, patience=None, Q=None, seed=1000):
+        self.name, self.mode, self.N, self.lanes, self.n_sets, self.n_steps = name, mode, int(N), int(lanes), int(n_sets), int(n_steps)
+        self.set_chains = SET_CHAINS_2 if self.lanes == 2 else SET_CHAINS
+        self.trace, self.patience, self.Q, self.seed = trace, patience, Q, int(seed)
+
+    @property
+    def n_chains(self):
+        return self.n_sets * self.set_chains
+
+    def seeds(self):
+        return abi.seeds_for(self.seed, self.n_chains)
+
+    def base_schedules(self):
+        """Every set its own mild linear schedule: what the steps nobody crafts run under."""
+        return [{"type": "linear_annealing", "beta_start": 0.2 + 0.05 * t, "beta_end": 0.9 + 0.1 * t} for t in range(self.n_sets)]
+
+    def base_table(self):
+        return np.ascontiguousarray(np.stack([abi.beta_values(sp, self.n_steps) for sp in self.base_schedules()]))
+
+    def params(self, table, flags=0, n_steps=None, first_step=0, patience="case", trace="case"):
+        """The Params block of the launch (or of its steps [first_step, first_step + n_steps)) under `table` ([n_sets][whole run]); the
+        block keeps the slice it points to alive."""
+        n = self.n_steps if n_steps is None else int(n_steps)
+        p = abi.make_params_sets(self.N, n, "random", self.base_schedules(), self.set_chains, mcmc_type=self.mode,
+                                 early_stop_patience=self.patience if patience == "case" else patience,
+                                 trace=self.trace if trace == "case" else trace, flags=flags, lanes_per_chain=self.lanes)
+        if self.Q is not None:
+            p.n_queens = int(self.Q)
+        tab = np.ascontiguousarray(np.asarray(table, dtype=np.float64)[:, first_step: first_step + n])
+        assert tab.shape == (self.n_sets, n)
+        p._schedules, p.beta_table, p._beta_keepalive = None, tab.ctypes.data, tab
+        return p
+
+
+# the launches the issue lists; `lanes` 0 = the library's default
+CASES = (
+    Case("board6_g2", "board", 6, 2, seed=1100, n_steps=450),
+    Case("board6_g4", "board", 6, 4, seed=1200, n_steps=317),
+    Case("board12_g4", "board", 12, 4, seed=1300, n_steps=330),
+    Case("board12_g8", "board", 12, 8, seed=1400, n_steps=351),
+    Case("board12_g16", "board", 12, 16, seed=1500, n_steps=470),
+    Case("board17_g8", "board", 17, 8, seed=1600, n_steps=333),
+    Case("board40", "board", 40, 0, seed=1700, n_steps=305),
+    Case("board12_notrace", "board", 12, 0, trace=False, seed=1800, n_steps=340),
+    Case("board12_reduced", "board", 12, 0, trace="reduced", seed=1900, n_steps=345),
+    Case("board12_patience", "board", 12, 0, patience=60, seed=2000, n_steps=400),
+    Case("full3d6_g8", "full_3d", 6, 8, seed=2100, n_steps=321),
+    Case("full3d10_g4", "full_3d", 10, 4, seed=2200, n_steps=338),
+    Case("full3d6_q20", "full_3d", 6, 0, Q=20, seed=2300, n_steps=310),
+    Case("full3d40", "full_3d", 40, 0, seed=2400, n_steps=300),
+)
+CASES_BY_NAME = {c.name: c for c in CASES}
+SEGMENT_CASES = ("board12_g4", "full3d6_g8")
+
+
+class _Streams:
+    """The raw 32-bit words of each seed's MT19937 stream, grown on demand."""
+
+    def __init__(self):
+        self.words = {}
+
+    def pair_before(self, seed, n_words):
+        have = self.words.get(seed)
+        if have is None or len(have) < n_words:
+            have = oracle.rng_stream(seed, "u32", max(int(n_words) + 4096, 2 * (0 if have is None else len(have))))
+            self.words[seed] = have
+        return int(have[n_words - 2]), int(have[n_words - 1])
+
+
+def _probe(case, streams, seed, row, s, patience):
+    """Chain `seed` under row[:s] and beta(s) = 0: (dE, u) of step s, or None when the chain does not execute step s as a step that appends
+    its entry (it stopped early)."""
+    tab = np.ascontiguousarray(row[: s + 1]).reshape(1, s + 1).copy()
+    tab[0, s] = 0.0
+    p = abi.make_params(case.N, s + 1, "random", case.base_schedules()[0], 1, mcmc_type=case.mode, early_stop_patience=patience, Q=case.Q)
+    p._schedules, p.beta_table = None, tab.ctypes.data
+    res = oracle.run(p, np.array([seed], dtype=np.uint32), states=False)
+    if int(res["hist_len"][0]) != s + 2:
+        return None
+    assert (int(res["accept_bits"][0, s >> 6]) >> (s & 63)) & 1, "beta = 0 accepts"
+    dE = int(res["energy_hist"][0, s + 1]) - int(res["energy_hist"][0, s])
+    return dE, uniform_of(*streams.pair_before(int(seed), int(res["stream_words"][0])))
+
+
+def _beta_for(spec, dE, u):
+    """beta with exp(-beta dE) at the wanted place next to u, or None.  spec: ("ulp", d) or ("rel", delta)."""
+    x = -math.log(u)
+    if dE <= 0 or not (X_MIN <= x <= X_MAX):
+        return None
+    if spec[0] == "rel":
+        beta = -math.log(u * (1.0 + spec[1])) / dE
+        prob = math.exp(-beta * dE)
+        rel = (prob - u) / u
+        if not (prob < 1.0 and abs(rel - spec[1]) <= 0.01 * abs(spec[1]) and abs(signed_ulps(prob, u)) > 1000):
+            return None
+        return beta
+    b0 = _bits(x / dE)
+    for k in range(2 * WALK + 1):
+        beta = _from_bits(b0 + ((k + 1) // 2 if k & 1 else -(k // 2)))
+        if signed_ulps(math.exp(-beta * dE), u) == spec[1]:
+            return beta
+    return None
+
+
+def _plan_for_set(case, t):
+    """The points set t is asked for, in step order: a tie for each of its chains (so that every lane group of a wavefront ties, at
+    every lane count), two more for one chain (it ties three times: the count adds up), and among them the near misses and this set's
+    share of the bracket points.  An early-stop case asks for fewer: its chains leave."""
+    n = case.set_chains
+    ties = [("count", ("ulp", COUNT_ULPS[(t + i) % 4]), (5 * t + i) % n) for i in range(n)]
+    thrice = ties[1][2]
+    ties.insert(2, ("count", ("ulp", COUNT_ULPS[(t + 1) % 4]), thrice))
+    ties.insert(3, ("count", ("ulp", COUNT_ULPS[(t + 2) % 4]), thrice))
+    others = [("miss", ("ulp", d), (3 * t + 7 * i + 2) % n) for i, d in enumerate(MISS_ULPS)]
+    others += [("bracket", ("rel", d), (t + 3 * i) % n) for i, d in enumerate(BRACKET_DELTAS) if i % case.n_sets == t % case.n_sets]
+    if case.patience is not None:
+        ties, others = ties[:8], others[:5]
+    plan, j = [], 0
+    for i, tie in enumerate(ties):  # interleaved: a tie, then now and then one of the others
+        plan.append(tie)
+        if j < len(others) and (i % 2 == 1 or len(ties) - i <= len(others) - j):
+            plan.append(others[j])
+            j += 1
+    return plan + others[j:]
+
+
+def craft(case, first_step=6, gap=4):
+    """(table [n_sets][n_steps], points): the case's base table with beta rewritten at the crafted steps, and one dict per crafted point --
+    set, chain (index in the launch), step, dE, u, beta, prob (math.exp(-beta dE)), accept (u < prob), kind, ulps (signed, as measured),
+    counts (1 where the oracle and the kernel must count a near tie)."""
+    table = case.base_table()
+    seeds, streams, points = case.seeds(), _Streams(), []
+    for t in range(case.n_sets):
+        row, s = table[t], first_step + t
+        for kind, spec, pos in _plan_for_set(case, t):
+            placed = False
+            for turn in range(case.set_chains):  # a chain that has stopped early hands over to its neighbour
+                c = t * case.set_chains + (pos + turn) % case.set_chains
+                while s < case.n_steps - 1:
+                    probe = _probe(case, streams, seeds[c], row, s, case.patience)
+                    if probe is None:
+                        break
+                    beta = _beta_for(spec, *probe)
+                    if beta is not None:
+                        placed = True
+                        break
+                    s += 1
+                if placed or s >= case.n_steps - 1:
+                    break
+            if not placed:
+                break
+            row[s] = beta
+            points.append(_point(t, c, s, probe[0], probe[1], beta, kind, 1 if kind == "count" else 0))
+            s += 1 + gap
+        if case.patience is not None:
+            points += _behind_the_stop(case, streams, seeds, table, t, s)
+    return table, points
+
+
+def _point(t, c, s, dE, u, beta, kind, counts):
+    prob = math.exp(-beta * dE)
+    return {"set": t, "chain": int(c), "step": int(s), "dE": int(dE), "u": u, "beta": beta, "prob": prob, "accept": bool(u < prob), "kind": kind,
+            "ulps": signed_ulps(prob, u), "counts": counts}
+
+
+def _behind_the_stop(case, streams, seeds, table, t, s):
+    """A +2 ulp tie for a chain of set t at a step behind its stop (found without early stopping, where the chain goes on): the step is
+    never executed under the case's patience."""
+    n = case.set_chains
+    sub = Case("set", case.mode, case.N, case.lanes, n_sets=1, n_steps=case.n_steps, patience=case.patience, seed=int(seeds[t * n]))
+    res = oracle.run(sub.params(table[t: t + 1]), seeds[t * n: (t + 1) * n], states=False)
+    stopped = [r for r in range(n) if int(res["steps_executed"][r]) <= s]
+    if not stopped:
+        return []
+    c, row = t * n + stopped[0], table[t]
+    while s < case.n_steps - 1:
+        probe = _probe(case, streams, seeds[c], row, s, None)
+        beta = _beta_for(("ulp", 2), *probe)
+        if beta is not None:
+            row[s] = beta
+            return [_point(t, c, s, probe[0], probe[1], beta, "behind", 0)]
+        s += 1
+    return []
+
+
+_crafted = {}
+
+
+def crafted(name):
+    """craft() of a listed case, once per process: the tests share it and leave it unchanged."""
+    if name not in _crafted:
+        table, points = craft(CASES_BY_NAME[name])
+        table.setflags(write=False)
+        _crafted[name] = (table, tuple(points))
+    return _crafted[name]
+
+
+def expected_near_ties(case, points):
+    want = np.zeros(case.n_chains, dtype=np.int64)
+    for pt in points:
+        want[pt["chain"]] += pt["counts"]
+    return want
+
+
+def kinds(points):
+    out = {}
+    for pt in points:
+        out[pt["kind"]] = out.get(pt["kind"], 0) + 1
+    return out
+
+
+def check_plan_was_met(case, points):
+    """What the issue asks of a case's points, so that a crafting that quietly places less fails here and not as a weaker test."""
+    ties = expected_near_ties(case, points)
+    per_set = [sum(1 for pt in points if pt["set"] == t) for t in range(case.n_sets)]
+    assert case.n_sets >= 4 and 300 <= case.n_steps <= 470 and min(per_set) >= 6, (case.name, per_set)
+    assert ties.sum() > 0 and ties.max() >= 3, f"{case.name}: no chain ties three times"
+    ulps = {pt["ulps"] for pt in points if pt["kind"] in ("count", "miss")}
+    assert ulps >= {2, -2, 3, -3, 8, -8}, (case.name, sorted(ulps))
+    for pt in points:
+        assert pt["kind"] != "count" or abs(pt["ulps"]) in (2, 3)
+        assert pt["kind"] != "miss" or abs(pt["ulps"]) == 8
+        assert pt["kind"] != "bracket" or abs(pt["ulps"]) > 1000
+        assert pt["accept"] == (pt["ulps"] > 0)
+    for d in (1, -1):
+        assert {pt["accept"] for pt in points if pt["kind"] == "count" and pt["ulps"] * d > 0} == {d > 0}
+    if case.patience is None:
+        positions = {pt["chain"] % case.set_chains for pt in points if pt["counts"]}
+        assert positions == set(range(case.set_chains)), f"{case.name}: chains {sorted(set(range(case.set_chains)) - positions)} of a set never tie"
+        got = sorted((pt["prob"] - pt["u"]) / pt["u"] for pt in points if pt["kind"] == "bracket")
+        want = sorted(BRACKET_DELTAS)
+        assert len(got) == len(want) and all(abs(g - w) <= 0.02 * abs(w) for g, w in zip(got, want)), f"{case.name}: bracket points {got}"
+    else:
+        assert any(pt["kind"] == "behind" for pt in points), f"{case.name}: no point behind a chain's stop"
+
+
+def accept_bit(res, chain, step):
+    return (int(res["accept_bits"][chain, step >> 6]) >> (step & 63)) & 1
+
+
+def first_difference(got, want, points, trace=True):
+    """Where two results part, for a failure message: the first (chain, step) whose history entry or accept bit differs (full trace) or the
+    first chain whose summary differs, and what was crafted there."""
+    at = {(pt["chain"], pt["step"]): pt for pt in points}
+    if trace is True:
+        best = None
+        for r in range(len(want["hist_len"])):
+            L = int(want["hist_len"][r])
+            for s in range(L - 1):
+                if int(got["energy_hist"][r, s + 1]) != int(want["energy_hist"][r, s + 1]) or accept_bit(got, r, s) != accept_bit(want, r, s):
+                    if best is None or s < best[1]:
+                        best = (r, s)
+                    break
+        if best is not None:
+            pt = at.get(best)
+            return (f"first difference at chain {best[0]}, step {best[1]}: " +
+                    (f"a crafted {pt['kind']} point ({pt['ulps']:+d} ulp, dE {pt['dE']}, u {pt['u']!r}, beta {pt['beta']!r})" if pt else "not a crafted point"))
+    for r in range(len(want["near_ties"])):
+        for k in ("near_ties", "n_accepted", "final_energy", "best_energy", "steps_to_best", "hist_len", "stream_words"):
+            if int(got[k][r]) != int(want[k][r]):
+                mine = [(pt["step"], pt["kind"], pt["ulps"]) for pt in points if pt["chain"] == r]
+                return f"first differing chain {r}: {k} {int(got[k][r])} != {int(want[k][r])}; crafted (step, kind, ulp) of that chain: {mine}"
+    return "no difference in histories, accept bits or summaries"

@@ -101,7 +101,7 @@ def assert_chain_equals_golden(res, r, case, gold, what):
 
 
 RESULT_FIELDS = ("hist_len", "steps_executed", "initial_energy", "best_energy", "final_energy", "steps_to_best",
-                 "n_accepted", "best_state", "final_state", "stream_words")
+                 "n_accepted", "best_state", "final_state", "stream_words", "near_ties")
 
 
 def assert_results_equal(a, b, what, trace=True):
