@@ -154,7 +154,12 @@ typedef struct mcq_params {
     int32_t n_queens;              /* full_3d only: Q queens instead of N*N (State3DQueens(N, Q=...), mcmc.py:6-18; metropolis_mcmc(..., Q=...),
                                       experiments.py:199-203), 2 <= Q < N^3, random init only (latin / klarner assume Q = N^2: mcmc.py:21-25);
                                       0 = N*N.  state_bytes becomes 3 Q (mcq_state_bytes_for). */
-    const double* exchange_ladder; /* HOST pointer (also for mcq_run_device), R finite positive multipliers.  Read during the call: validated, and copied to the
+    const double* exchange_ladder; /* HOST pointer (also for mcq_run_device), R positive multipliers, each within float32's normal range
+                                      [2^-126, 2^127 (2 - 2^-23)]: the sweep's float32 bracket of the accept test runs at (float)ladder[t], which
+                                      must be neither 0 nor infinity; anything else is MCQ_EINVAL, in the oracle too.  What remains: under exchange
+                                      a |beta(step)| beyond float32's range is followed through its float32 image (0 or infinity) in the bracket,
+                                      where beta(step) * ladder[t] may still be an ordinary number; without exchange there is no such limit (a beta
+                                      whose image is 0 or infinity has exp(-beta dE) = 1 or 0 in float64 as well).  Read during the call: validated, and copied to the
                                       device with a hipMemcpyAsync on the caller's stream from THIS (normally pageable) array, so it must stay valid until
                                       that copy has run -- mcq_run_host and the Python wrappers keep it alive and synchronise; a caller of mcq_run_device
                                       keeps it until the stream has passed the call (with exchange the call cannot be part of a stream capture) */

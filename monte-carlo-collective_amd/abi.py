@@ -588,6 +588,11 @@ def set_stream_states(params, states):
     return params
 
 
+# include/mcq.h, exchange_ladder: the sweep's bracket works on the float32 image of a multiplier, so it must be a normal float32 number
+LADDER_MIN, LADDER_MAX = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
+LADDER_RANGE_ERROR = "exchange_ladder entries must be finite and positive, within float32's normal range [2^-126, 2^127 (2 - 2^-23)]"
+
+
 def set_exchange(params, every, ladder):
     """Turn on replica exchange (include/mcq.h: exchange_every / exchange_replicas / exchange_ladder) on a Params block:
     every `every` steps neighbouring rungs of each ladder of len(ladder) consecutive chains are offered a swap of their beta
@@ -599,6 +604,8 @@ def set_exchange(params, every, ladder):
         raise ValueError("the exchange ladder has 2, 4, 8 or 16 rungs")
     if params.n_chains % len(lad) or (params.n_sets > 1 and params.chains_per_set % len(lad)):
         raise ValueError("n_chains (and chains_per_set) must be multiples of the number of rungs")
+    if not np.all((lad >= LADDER_MIN) & (lad <= LADDER_MAX)):  # NaN fails both compares
+        raise ValueError(LADDER_RANGE_ERROR)
     params.exchange_every, params.exchange_replicas = int(every), len(lad)
     params.exchange_ladder = lad.ctypes.data_as(C.POINTER(C.c_double))
     params._ladder_keepalive = lad

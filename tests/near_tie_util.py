@@ -300,10 +300,22 @@ def accept_bit(res, chain, step):
     return (int(res["accept_bits"][chain, step >> 6]) >> (step & 63)) & 1
 
 
+def _swap_point_behind(points, chain, step):
+    """The last crafted swap point (tests/exchange_tie_util.py) in front of `step` in which `chain` took part, described -- a swap that
+    went the other way shows in the histories only at a later step of one of the two chains."""
+    mine = [pt for pt in points if pt.get("what") == "swap" and chain in (pt["chain"], pt["partner"]) and (step is None or pt["step"] < step)]
+    if not mine:
+        return "no crafted swap point of that chain in front of it"
+    pt = max(mine, key=lambda pt: pt["step"])
+    return (f"the last crafted swap point of that chain in front of it: after step {pt['step']}, {pt['kind']} ({pt['ulps']:+d} ulp), chains {pt['chain']} (rung "
+            f"{pt['t']}, counts the tie) and {pt['partner']}, E_a - E_b {pt['dEab']}, u {pt['u']!r}, beta {pt['beta']!r}, swap {pt['swap']}")
+
+
 def first_difference(got, want, points, trace=True):
     """Where two results part, for a failure message: the first (chain, step) whose history entry or accept bit differs (full trace) or the
-    first chain whose summary differs, and what was crafted there."""
-    at = {(pt["chain"], pt["step"]): pt for pt in points}
+    first chain whose summary differs, and what was crafted there; under replica exchange also the crafted swap point behind it."""
+    at = {(pt["chain"], pt["step"]): pt for pt in points if pt.get("what") != "swap"}
+    swaps = any(pt.get("what") == "swap" for pt in points)
     if trace is True:
         best = None
         for r in range(len(want["hist_len"])):
@@ -316,10 +328,12 @@ def first_difference(got, want, points, trace=True):
         if best is not None:
             pt = at.get(best)
             return (f"first difference at chain {best[0]}, step {best[1]}: " +
-                    (f"a crafted {pt['kind']} point ({pt['ulps']:+d} ulp, dE {pt['dE']}, u {pt['u']!r}, beta {pt['beta']!r})" if pt else "not a crafted point"))
+                    (f"a crafted {pt['kind']} point ({pt['ulps']:+d} ulp, dE {pt['dE']}, u {pt['u']!r}, beta {pt['beta']!r})" if pt else "not a crafted point") +
+                    (f"; {_swap_point_behind(points, best[0], best[1])}" if swaps else ""))
+    fields = ("near_ties", "n_accepted", "final_energy", "best_energy", "steps_to_best", "hist_len", "stream_words") + (("exchange_rung", "n_exchanges") if swaps else ())
     for r in range(len(want["near_ties"])):
-        for k in ("near_ties", "n_accepted", "final_energy", "best_energy", "steps_to_best", "hist_len", "stream_words"):
+        for k in fields:
             if int(got[k][r]) != int(want[k][r]):
-                mine = [(pt["step"], pt["kind"], pt["ulps"]) for pt in points if pt["chain"] == r]
-                return f"first differing chain {r}: {k} {int(got[k][r])} != {int(want[k][r])}; crafted (step, kind, ulp) of that chain: {mine}"
+                mine = [(pt["step"], pt.get("what", "step"), pt["kind"], pt["ulps"]) for pt in points if r in (pt["chain"], pt.get("partner"))]
+                return f"first differing chain {r}: {k} {int(got[k][r])} != {int(want[k][r])}; crafted (step, what, kind, ulp) of that chain: {mine}"
     return "no difference in histories, accept bits or summaries"

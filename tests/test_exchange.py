@@ -153,12 +153,23 @@ def test_exchange_parameter_errors():
     r = abi.make_params(6, 10, "random", SP, 8, mcmc_type="board", early_stop_patience=None, trace="reduced")
     abi.set_exchange(r, 2, np.ones(4))
     assert L.mcq_workspace_bytes(ctypes.byref(r)) == 0 and b"trace none or i32" in L.mcq_last_error()
-    # a rung runs at beta(step) * ladder[t]: multipliers that are not positive finite numbers are refused by both libraries
-    for bad in (0.0, -1.0, float("nan"), float("inf")):
-        b = abi.set_exchange(abi.make_params(6, 10, "random", SP, 8, mcmc_type="board", early_stop_patience=None), 2, [1.0, bad, 1.2, 1.4])
-        with pytest.raises(ValueError, match="finite and positive"):
+    # a rung runs at beta(step) * ladder[t], and the bracket of the accept test at the float32 image of ladder[t]: multipliers that are not
+    # positive normal float32 numbers are refused by both libraries and by abi.set_exchange, with one message
+    tiny, top = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
+    for bad in (0.0, -1.0, float("nan"), float("inf"), 1e40, 1e-50, np.nextafter(tiny, 0.0), np.nextafter(top, np.inf)):
+        fresh = lambda: abi.make_params(6, 10, "random", SP, 8, mcmc_type="board", early_stop_patience=None)  # noqa: E731
+        with pytest.raises(ValueError, match="finite and positive") as e:
+            abi.set_exchange(fresh(), 2, [1.0, bad, 1.2, 1.4])
+        message = str(e.value)
+        assert "float32's normal range" in message
+        b, lad = abi.set_exchange(fresh(), 2, [1.0, 1.1, 1.2, 1.4]), np.array([1.0, bad, 1.2, 1.4])
+        b.exchange_ladder, b._ladder_keepalive = lad.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), lad  # past the wrapper's own check
+        with pytest.raises(ValueError, match="finite and positive") as e:
             oracle.run(b, abi.seeds_for(1, 8))
-        assert L.mcq_workspace_bytes(ctypes.byref(b)) == 0 and b"finite and positive" in L.mcq_last_error()
+        assert str(e.value) == message
+        assert L.mcq_workspace_bytes(ctypes.byref(b)) == 0 and L.mcq_last_error().decode() == message
+    ends = abi.set_exchange(abi.make_params(6, 10, "random", SP, 8, mcmc_type="board", early_stop_patience=None), 2, [tiny, 1.0, 1.2, top])
+    assert L.mcq_workspace_bytes(ctypes.byref(ends)) > 0 and int(oracle.run(ends, abi.seeds_for(1, 8))["hist_len"][0]) == 11
 
 
 # ---- HIP == oracle ---------------------------------------------------------------------------------------------------------
@@ -217,3 +228,36 @@ def test_hip_exchange_ladder_too_wide_for_the_lane_count():
     p = _params(12, 100, 64, "board", 8, _ladder(16), lanes_per_chain=8)
     with pytest.raises(ValueError, match="lanes_per_chain"):
         mcq_amd._lib.run_host(p, abi.seeds_for(3, 64))
+
+
+# ---- the ladder at the ends of what the kernel's float32 image of it carries -------------------------------------------------
+# beta cycles through these, step by step: 0, ordinary, huge and tiny; and a second table whose huge and tiny values times a multiplier
+# beyond float32's range (1e40, 1e-50: refused, test_exchange_parameter_errors) would be ordinary numbers -- with those two ladders the
+# bracket followed infinity and 0 instead, and the kernels parted from the oracle under this table (not under the first)
+RANGE_TABLES = {"0, 1, 2^120, 2^-120": (0.0, 1.0, 2.0 ** 120, 2.0 ** -120), "0, 1, 2^-133, 2^166": (0.0, 1.0, 2.0 ** -133, 2.0 ** 166)}
+RANGE_LADDERS = {"2^-120 .. 2^120": (2.0 ** -120, 1.0, 1.3, 2.0 ** 120), "2^-126 .. 2^127": (2.0 ** -126, 0.7, 1.0, 2.0 ** 127)}
+
+
+def _range_params(ladder, table, flags=0):
+    n_steps = 400
+    tab = np.ascontiguousarray(np.resize(np.asarray(table, dtype=np.float64), n_steps))
+    p = _params(6, n_steps, 64, "board", 3, ladder, flags=flags)
+    p._schedules, p.beta_table, p._beta_keepalive = None, tab.ctypes.data, tab
+    return p
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("table", list(RANGE_TABLES))
+@pytest.mark.parametrize("name", list(RANGE_LADDERS))
+def test_hip_exchange_ladder_at_the_ends_of_float32(name, table):
+    """Multipliers at the ends of float32's normal range -- the widest the libraries accept: the bracket works on the float32 image of
+    the ladder -- under a table whose beta is 0, ordinary, huge and tiny in turn: every output is the oracle's, bracketed and with
+    MCQ_FLAG_EXACT_EXP."""
+    seeds = abi.seeds_for(77, 64)
+    want = oracle.run(_range_params(RANGE_LADDERS[name], RANGE_TABLES[table]), seeds, fast=True, n_threads=4)
+    assert int(want["n_exchanges"].sum()) > 0 and 0 < int(want["n_accepted"].sum()) < 64 * 400
+    for flags in (0, abi.FLAG_EXACT_EXP):
+        got, _ = mcq_amd._lib.run_host(_range_params(RANGE_LADDERS[name], RANGE_TABLES[table], flags=flags), seeds)
+        util.assert_results_equal(got, want, f"ladder {name}, table {table}, flags {flags}")
+        for k in EX_FIELDS:
+            np.testing.assert_array_equal(got[k], want[k], err_msg=f"ladder {name}, table {table}, flags {flags}: {k}")
