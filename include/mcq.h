@@ -695,6 +695,100 @@ int mcq_heatbath3d_device(const mcq_heatbath3d* q, void* hip_stream);
  * index and the value. */
 int mcq_heatbath3d_host(const mcq_heatbath3d* q);
 
+/*
+ * Parallel tempering of board heat-bath sweeps, one ladder per workgroup (csrc/mcq_temper.hip) -- NOT a mode of the reference, never a
+ * default, like Philox, replica exchange in the Metropolis sweep (mcq_params.exchange_*), population annealing, the quenches and the
+ * heat baths.  The replicas of a ladder run mcq_heatbath's sweep at different beta and trade their temperatures between sweeps, in ONE
+ * launch: mcq_heatbath takes one table row per sweep for every chain of a launch, and chains of different workgroups cannot meet
+ * without ending the kernel.  Boards only.  The rule is integer-exact, with no floating point on the device:
+ *   1. ladders: R = replicas is 2, 4, 8 or 16 and divides n_chains; ladder g holds the chain slots [g R, (g + 1) R).  A slot keeps its
+ *      placement, its seed, its Philox stream, its best values and its history for the whole run; what moves between the slots of a
+ *      ladder is the RUNG t = 0 .. R - 1.  rung_in (optional) gives every slot's starting rung and must hold a permutation of 0 .. R - 1
+ *      per ladder; NULL means slot r starts on rung r mod R.  rung_out (optional) returns the final rungs.
+ *   2. the sweep: a call runs n_sweeps sweeps; sweep s of the call has the global index g = first_sweep + s and is the sweep of the
+ *      mcq_heatbath rule above, items 1 - 6, unchanged except for the table row: a slot on rung t uses the row T[s][t] of `table`
+ *      (uint32 [n_sweeps][R][table_len]).  Unchanged means the same clamping, the same a(c, k), the same column order, the same word
+ *      w = g N^2 + c of the Philox stream with key (seeds[slot], 1), the same U and selection, the same best values at sweep ends
+ *      (before the sweep's event) and the same energy_hist.  A ladder whose R rows are equal is therefore R plain heat-bath chains,
+ *      whatever the exchanges do.
+ *   3. the exchange: exchange_every = K >= 1.  After the sweep with global index g an EVENT happens when (g + 1) mod K = 0; its global
+ *      index is e = (g + 1) / K - 1.  The event looks at the pairs of neighbouring rungs (t, t + 1) with t = e (mod 2) and t + 1 < R.
+ *      With a the slot on rung t, b the slot on rung t + 1 and Delta = E_b - E_a, the running energies after that sweep:
+ *        Delta >= 0  the colder rung holds the higher energy (or the same): the two slots swap rungs;
+ *        Delta <  0  d = -Delta, and they swap when x < X[j][t][min(d, DX - 1)],
+ *      where `swap_table` is uint32 [n_events][R - 1][swap_len], j = e - floor(first_sweep / K) is the event's index within the call,
+ *      DX = swap_len (1 .. MCQ_MAX_TEMPER_SWAP_TABLE), and x is the word e R + t (64-bit) of the stream
+ *      word w = philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[g R], 3))[w % 4] -- the seed of
+ *      the ladder's slot 0; key words 0, 1 and 2 are taken by MCQ_RNG_PHILOX4X32_10 of the sweep and the two heat baths.  The pairs of
+ *      an event are disjoint, so their order does not matter.  x is drawn only where Delta < 0 (a stream addressed by position).
+ *      n_events = floor((first_sweep + n_sweeps) / K) - floor(first_sweep / K), and the caller must say as many;
+ *      floor((first_sweep + n_sweeps) / K) R must stay below 2^63.
+ *   4. the Python side builds T[s][t][d] = floor(2^24 exp(-beta_s l_t d)) (the rows of mcq_heatbath at beta_s l_t) and
+ *      X[j][t][d] = min(2^32 - 1, floor(2^32 exp(-beta_g (l_{t+1} - l_t) d))), g the sweep the event follows, from multipliers
+ *      0 < l_0 <= l_1 <= .. <= l_{R-1}: rung R - 1 is the coldest, and the swap probability min(1, exp((beta_b - beta_a)(E_b - E_a)))
+ *      of replica exchange is 1 for Delta >= 0, which is why the table is one-sided.  A caller's own tables are as good; every entry
+ *      of T is at most 2^MCQ_HEATBATH_WEIGHT_BITS.
+ *   5. outputs per slot: those of mcq_heatbath (relative to the call, as there), rung_out, n_exchanges (the swaps of this call the slot
+ *      took part in) and rung_hist (optional, uint8 [n_chains][hist_stride]: entry 0 the starting rung, entry s + 1 the rung after
+ *      sweep s and its event).  Per ladder: pair_accepted (optional, int64 [n_chains / R][R - 1]: the swaps of this call per pair of
+ *      rungs (t, t + 1)), which a caller needs to tune a ladder.  The sum of n_exchanges over a ladder is twice that of pair_accepted.
+ *   6. so: the state of a ladder is its placements, its rungs and a sweep index, and nothing else: a run cut into calls with
+ *      first_sweep, the placements and the rungs carried over (and the rows of both tables split accordingly) is the unbroken run.
+ *      K > n_sweeps + first_sweep gives no event: each slot is then a plain heat-bath chain at its own rung's rows.  state_out may be
+ *      state_in (the slots of a ladder meet through their energies only).
+ */
+#define MCQ_MAX_TEMPER_SWAP_TABLE 4096
+#define MCQ_MAX_TEMPER_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_temper_device may take */
+
+typedef struct mcq_temper {
+    int32_t N;             /* MCQ_MIN_N .. MCQ_MAX_N_BOARD (mcq_temper_device: as far as a ladder fits the LDS, see below) */
+    int32_t mode;          /* MCQ_MODE_BOARD; full_3d is MCQ_EINVAL */
+    int64_t n_chains;      /* 1 .. 2^31 - 1, a multiple of replicas */
+    int64_t n_sweeps;      /* >= 0 */
+    int64_t first_sweep;   /* >= 0: global index of the call's sweep 0; (first_sweep + n_sweeps) N^2 < 2^63 */
+    int64_t replicas;      /* R: 2, 4, 8 or 16 */
+    int64_t exchange_every; /* K >= 1 */
+    int64_t n_events;      /* floor((first_sweep + n_sweeps) / K) - floor(first_sweep / K): the rows of swap_table */
+    const uint32_t* seeds; /* [n_chains] */
+    const uint32_t* table; /* [n_sweeps][R][table_len]: T; may be NULL when n_sweeps = 0 */
+    int64_t table_len;     /* D, 1 .. MCQ_MAX_HEATBATH_TABLE */
+    const uint32_t* swap_table; /* [n_events][R - 1][swap_len]: X; may be NULL when n_events = 0 */
+    int64_t swap_len;      /* DX, 1 .. MCQ_MAX_TEMPER_SWAP_TABLE */
+    const uint8_t* rung_in; /* optional [n_chains]: a permutation of 0 .. R - 1 per ladder; NULL = slot r on rung r mod R */
+    uint8_t* rung_out;     /* optional [n_chains] */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;    /* [n_chains][N*N]; may be state_in */
+    int32_t* energy_in;    /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;   /* optional [n_chains] */
+    int32_t* best_energy;  /* optional [n_chains] */
+    int64_t* best_sweep;   /* optional [n_chains] */
+    uint8_t* best_state;   /* optional [n_chains][N*N]; neither state_in nor state_out */
+    int64_t* n_changed;    /* optional [n_chains] */
+    int32_t* energy_hist;  /* optional [n_chains][hist_stride] */
+    int64_t hist_stride;   /* entries per chain row of energy_hist and of rung_hist, >= n_sweeps + 1 (read only when one of them is given) */
+    int64_t* n_exchanges;  /* optional [n_chains] */
+    uint8_t* rung_hist;    /* optional [n_chains][hist_stride] */
+    int64_t* pair_accepted; /* optional [n_chains / R][R - 1] */
+} mcq_temper;
+
+/* the message of the last error of the calling thread from the two mcq_temper_* calls below (they do not set mcq_last_error()) */
+const char* mcq_temper_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  ONE kernel enqueued on `hip_stream`, a workgroup per ladder (two ladders where one is
+ * narrower than a wavefront), the exchange through LDS and two barriers; asynchronous: nothing is copied back and nothing synchronises.
+ * MCQ_EINVAL before any launch and without touching a device: what mcq_heatbath_device refuses of the fields the two blocks share;
+ * replicas other than 2, 4, 8, 16 or not dividing n_chains; exchange_every < 1; an n_events other than rule item 3 gives;
+ * floor((first_sweep + n_sweeps) / K) R >= 2^63; swap_len outside 1 .. MCQ_MAX_TEMPER_SWAP_TABLE; a NULL swap_table with n_events > 0;
+ * hist_stride < n_sweeps + 1 with energy_hist or rung_hist given; and a ladder whose LDS -- per ladder 6 NP^2 R bytes of placements (NP = N rounded up to
+ * 8, 12, 16, 24, 32 or 64), 4 R table_len bytes of staged rows and 12 R bytes for the event -- exceeds MCQ_MAX_TEMPER_LDS: N = 33 .. 64 with R >= 8, and every
+ * N > 64; the message names N, R and the bytes.  NOT checked, being on the device: what mcq_heatbath_device does not check of T, and
+ * rung_in -- a rung is clamped to R - 1, and a ladder whose rungs are no permutation gets outputs that are not the rule's; nothing
+ * leaves the arrays. */
+int mcq_temper_device(const mcq_temper* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, for every N up to MCQ_MAX_N_BOARD (no LDS here); needs no GPU.  Equal to the
+ * kernel bit for bit on every output.  It reads its inputs, so it also refuses with MCQ_EINVAL an entry of T above
+ * 2^MCQ_HEATBATH_WEIGHT_BITS and a rung_in that is no permutation of 0 .. R - 1 in some ladder; the message names the place. */
+int mcq_temper_host(const mcq_temper* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -202,6 +202,11 @@ def lib():
         L.mcq_heatbath3d_device.argtypes = [C.POINTER(abi.Heatbath3D), C.c_void_p]
         L.mcq_heatbath3d_host.restype = C.c_int
         L.mcq_heatbath3d_host.argtypes = [C.POINTER(abi.Heatbath3D)]
+        L.mcq_temper_last_error.restype = C.c_char_p
+        L.mcq_temper_device.restype = C.c_int
+        L.mcq_temper_device.argtypes = [C.POINTER(abi.Temper), C.c_void_p]
+        L.mcq_temper_host.restype = C.c_int
+        L.mcq_temper_host.argtypes = [C.POINTER(abi.Temper)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -323,6 +328,28 @@ def heatbath3d_host(q):
 def heatbath3d_device(q, stream):
     """mcq_heatbath3d_device on a filled abi.Heatbath3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_heatbath3d(lib().mcq_heatbath3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_temper(rc):
+    """_check for the mcq_temper_* calls, which keep their own message (mcq_temper_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_temper_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def temper_host(q):
+    """mcq_temper_host on a filled abi.Temper block of HOST pointers.  Pure host code, no GPU."""
+    _check_temper(lib().mcq_temper_host(C.byref(q)))
+
+
+def temper_device(q, stream):
+    """mcq_temper_device on a filled abi.Temper block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_temper(lib().mcq_temper_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def resample_plan_host(energies, population, table, offsets):

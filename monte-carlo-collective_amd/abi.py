@@ -272,6 +272,106 @@ class Heatbath3D(C.Structure):
 HEATBATH3D_DTYPES = dict(HEATBATH_DTYPES, flags=np.int32)
 
 
+MAX_TEMPER_SWAP_TABLE = 4096   # include/mcq.h: MCQ_MAX_TEMPER_SWAP_TABLE
+MAX_TEMPER_LDS = 160 * 1024    # MCQ_MAX_TEMPER_LDS
+TEMPER_REPLICAS = (2, 4, 8, 16)
+
+
+class Temper(C.Structure):
+    """include/mcq.h: mcq_temper -- parallel tempering of board heat-bath sweeps, one ladder per workgroup"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_sweeps", C.c_int64),
+        ("first_sweep", C.c_int64),
+        ("replicas", C.c_int64),
+        ("exchange_every", C.c_int64),
+        ("n_events", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("table", C.c_void_p),
+        ("table_len", C.c_int64),
+        ("swap_table", C.c_void_p),
+        ("swap_len", C.c_int64),
+        ("rung_in", C.c_void_p),
+        ("rung_out", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_sweep", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_changed", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("n_exchanges", C.c_void_p),
+        ("rung_hist", C.c_void_p),
+        ("pair_accepted", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a tempered call besides the placements: field -> dtype (pair_accepted has a row of R - 1 per ladder)
+TEMPER_DTYPES = dict(HEATBATH_DTYPES, rung_out=np.uint8, n_exchanges=np.int64)
+
+
+def temper_events(first_sweep, n_sweeps, exchange_every):
+    """The exchange events of a call (include/mcq.h, tempering rule, item 3): floor((first_sweep + n_sweeps) / K) - floor(first_sweep / K)."""
+    K = int(exchange_every)
+    if K < 1:
+        raise ValueError(f"exchange_every must be >= 1, got {exchange_every}")
+    return (int(first_sweep) + int(n_sweeps)) // K - int(first_sweep) // K
+
+
+def temper_ladder(ladder):
+    """The multipliers l_0 <= .. <= l_{R-1} of a ladder as float64, checked: R in TEMPER_REPLICAS, finite, positive, non-decreasing (the
+    one-sided swap table needs beta non-decreasing in the rung: rung R - 1 is the coldest)."""
+    l = np.ascontiguousarray(ladder, dtype=np.float64).reshape(-1)
+    if len(l) not in TEMPER_REPLICAS:
+        raise ValueError(f"a ladder has 2, 4, 8 or 16 multipliers, got {len(l)}")
+    if not (np.isfinite(l).all() and (l > 0.0).all()):
+        raise ValueError("the multipliers of a ladder must be finite and positive")
+    if (np.diff(l) < 0.0).any():
+        raise ValueError("the multipliers of a ladder must be non-decreasing: a decreasing step would put the colder replica on the lower rung")
+    return l
+
+
+def temper_tables(betas, ladder, exchange_every=1, first_sweep=0):
+    """Both tables of a tempered call (include/mcq.h, tempering rule, item 4), NumPy's exp / floor on float64:
+      T uint32[n_sweeps][R][D]       T[s][t][d] = floor(2^24 exp(-beta_s l_t d)), the rows of heatbath_table at beta_s l_t; D as there;
+      X uint32[n_events][R - 1][DX]  X[j][t][d] = min(2^32 - 1, floor(2^32 exp(-beta_g (l_{t+1} - l_t) d))), g the sweep event j follows;
+                                     DX = 1 + the first d with X = 0 over the rows, at most MAX_TEMPER_SWAP_TABLE.
+    A row of X whose exponent is 0 (beta_g = 0, or two equal multipliers) is constant and reads the same at every length; a positive
+    exponent too small for the zero to arrive within MAX_TEMPER_SWAP_TABLE entries is a ValueError that names it: the kernel clamps d
+    to DX - 1, and that entry must be the one every larger d has.  No sweep gives T = [[[2^24]] * R]; no event gives X of no rows."""
+    l = temper_ladder(ladder)
+    R = len(l)
+    b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+    n_events = temper_events(first_sweep, b.size, exchange_every)  # (refuses K < 1)
+    if int(first_sweep) < 0:
+        raise ValueError(f"first_sweep must be >= 0, got {first_sweep}")
+    if not (np.isfinite(b).all() and (b >= 0.0).all()):
+        raise ValueError("the heat-bath sweep needs finite beta >= 0 for every sweep")
+    if not np.isfinite(b[:, None] * l[None, :]).all():
+        raise ValueError("beta times a ladder multiplier overflows")
+    T = heatbath_table(b[:, None] * l[None, :]).reshape(max(b.size, 1), R if b.size else 1, -1)
+    if b.size == 0:
+        T = np.ascontiguousarray(np.repeat(T, R, axis=1))
+    K = int(exchange_every)
+    g = (int(first_sweep) // K + 1 + np.arange(n_events, dtype=np.int64)) * K - 1 - int(first_sweep)  # the call's sweep each event follows
+    x = b[g][:, None] * np.diff(l)[None, :]  # [n_events][R - 1] exponents per unit of energy
+    d = np.arange(MAX_TEMPER_SWAP_TABLE, dtype=np.float64)
+    X = np.minimum(np.floor(4294967296.0 * np.exp(-x[:, :, None] * d[None, None, :])), 4294967295.0).astype(np.uint32)
+    bad = (x > 0.0) & (X[:, :, -1] != 0)
+    if bad.any():
+        j, t = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f"the ladder step l[{t + 1}] - l[{t}] = {l[t + 1] - l[t]:g} at beta = {b[g[j]]:g} (sweep {int(first_sweep) + int(g[j])}) is too small: "
+                         f"exp(-{x[j, t]:g} d) does not reach 0 in 32 bits within swap_len = {MAX_TEMPER_SWAP_TABLE} entries")
+    live = X[x > 0.0].reshape(-1, MAX_TEMPER_SWAP_TABLE)
+    support = int((live != 0).any(axis=0).sum()) if live.size else 0  # the rows fall monotonically: the first all-zero d
+    return T, np.ascontiguousarray(X[:, :, : min(support + 1, MAX_TEMPER_SWAP_TABLE)])
+
+
 class PackSlot(C.Structure):
     """include/mcq.h: mcq_pack_slot -- where one job's fields sit in the packed summary tensor (word offsets, -1 = absent)"""
     _fields_ = [("counters", C.c_int64), ("min_slot", C.c_int64), ("best", C.c_int64), ("stb", C.c_int64), ("stats", C.c_int64)]
