@@ -700,7 +700,7 @@ int mcq_heatbath3d_host(const mcq_heatbath3d* q);
  * default, like Philox, replica exchange in the Metropolis sweep (mcq_params.exchange_*), population annealing, the quenches and the
  * heat baths.  The replicas of a ladder run mcq_heatbath's sweep at different beta and trade their temperatures between sweeps, in ONE
  * launch: mcq_heatbath takes one table row per sweep for every chain of a launch, and chains of different workgroups cannot meet
- * without ending the kernel.  Boards only.  The rule is integer-exact, with no floating point on the device:
+ * without ending the kernel.  Boards only (full_3d placements: mcq_temper3d below).  The rule is integer-exact, with no floating point on the device:
  *   1. ladders: R = replicas is 2, 4, 8 or 16 and divides n_chains; ladder g holds the chain slots [g R, (g + 1) R).  A slot keeps its
  *      placement, its seed, its Philox stream, its best values and its history for the whole run; what moves between the slots of a
  *      ladder is the RUNG t = 0 .. R - 1.  rung_in (optional) gives every slot's starting rung and must hold a permutation of 0 .. R - 1
@@ -788,6 +788,96 @@ int mcq_temper_device(const mcq_temper* q, void* hip_stream);
  * kernel bit for bit on every output.  It reads its inputs, so it also refuses with MCQ_EINVAL an entry of T above
  * 2^MCQ_HEATBATH_WEIGHT_BITS and a rung_in that is no permutation of 0 .. R - 1 in some ladder; the message names the place. */
 int mcq_temper_host(const mcq_temper* q);
+
+/*
+ * Parallel tempering of full_3d heat-bath queen sweeps, one ladder per workgroup (csrc/mcq_temper3d.hip) -- NOT a mode of the reference,
+ * never a default, like everything above that is labelled so.  The replicas of a ladder run mcq_heatbath3d's sweep at different beta, each
+ * on an attack field of its own, and trade their temperatures between sweeps, in ONE launch.  mcq_temper above keeps refusing full_3d;
+ * this block has its own entry points.  The rule is integer-exact, with no floating point on the device:
+ *   1. ladders: as in the mcq_temper rule, item 1.  R = replicas is 2, 4, 8 or 16 and divides n_chains; ladder g holds the chain slots
+ *      [g R, (g + 1) R).  A slot keeps its placement, its seed, its stream, its best values and its histories; what moves is the RUNG.
+ *      rung_in and rung_out are as there.
+ *   2. the sweep is that of the mcq_heatbath3d rule, items 1 - 7, unchanged except for the table row: a slot on rung t uses the row
+ *      T[s][t] of `table` (uint32 [n_sweeps][R][table_len]).  Unchanged means the same clamping, the same cell order, the same update
+ *      word u = g Q + q of the stream with key (seeds[slot], 2), the same U and selection, the same W = 0 case, and the same best values
+ *      at sweep ends (taken before the sweep's event).  A ladder whose R rows are equal is therefore R plain mcq_heatbath3d chains,
+ *      whatever the exchanges do.
+ *   3. the exchange is that of the mcq_temper rule, item 3, verbatim -- the event after the sweep with global index g when
+ *      (g + 1) mod K = 0, the pairs t = e (mod 2), Delta >= 0 always swaps and otherwise x < X[j][t][min(-Delta, DX - 1)], x the word
+ *      e R + t -- with one change: the key of the stream is (seeds[g R], 4); key words 0 - 3 are taken by the sweep, the two heat baths
+ *      and mcq_temper.  The bounds on n_events, swap_len and the word index are the same.
+ *   4. a REPEATED placement (two queens in one cell after clamping) cannot enter a byte field.  If any slot of a ladder holds one, the
+ *      whole ladder is HELD, handed back unmoved: every slot gets state_out = best_state = the clamped input, energy_in = energy_out =
+ *      best_energy = the pairwise recount (a shared cell counts as a pair), best_sweep = n_changed = n_exchanges = 0, rung_out = its
+ *      starting rung, every entry of energy_hist the recount and every entry of rung_hist the starting rung; the ladder's row of
+ *      pair_accepted is 0.  flags bit 0 (MCQ_HEATBATH3D_REPEATED) is set on the slots that hold a repeat, bit 1 (MCQ_TEMPER3D_HELD) on
+ *      every slot of such a ladder.  The host code and the kernel do the same (it keeps every barrier of the kernel uniform over the
+ *      workgroup).  Other ladders of the call run normally.
+ *   5. outputs, segments and K > number of sweeps: as in the mcq_temper rule, items 5 - 6.  The state of a ladder is its placements, its
+ *      rungs and a sweep index: a run cut into calls with those carried over, and the rows of both tables split accordingly, is the
+ *      unbroken run.  state_out may be state_in.
+ * The tables are those of mcq_temper, item 4: T[s][t][d] = floor(2^24 exp(-beta_s l_t d)), a <= 403 < 512.
+ *
+ * mcq_temper3d_device keeps a ladder in the LDS of one workgroup: per chain 72 dwords of its own (minimum, scan, winner), the field
+ * (one byte per cell to N = 19, 16 bits beyond), the occupancy bitmap and the queens (16 bits each), rounded up to 4 dwords; R D dwords
+ * of staged table rows; 3 R words for the event:
+ *   bytes = 4 (R roundup4(72 + fw + bw + ceil(Q / 2)) + R D + 3 R) <= MCQ_MAX_TEMPER_LDS - MCQ_TEMPER3D_STATIC_LDS,
+ *   fw = ceil(N^3 / (4 or 2)),  bw = ceil(N^3 / 32); the workgroup-wide OR behind "some slot repeats" keeps 256 bytes of static LDS.
+ * With Q = N^2 and D = 512 (a shorter table lets a slightly larger N in) the largest N of each R, and its bytes:
+ *      R = 16   N = 18   153 024          R = 4   N = 25   147 248
+ *      R = 8    N = 20   161 248          R = 2   N = 32   148 056
+ * (N = 12, R = 16 with Q = N^3 - 1 = 1727: 124 096.)  A chain is W = min(64 | 256 | 1024 for N <= 12 | <= 19 | <= 32, 1024 / R) lanes; a
+ * lane adds the weights of (ceil(fw / W) | 1) cells-per-dword cells in 32 bits, at most 108 cells in what fits the LDS (N = 19, R = 16,
+ * which fits with a table shorter than 512), and 255 entries of 2^24 stay below 2^32.
+ */
+#define MCQ_TEMPER3D_STATIC_LDS 256 /* bytes of static LDS of the kernel, which count against MCQ_MAX_TEMPER_LDS */
+#define MCQ_TEMPER3D_HELD 2 /* flags bit 1: a slot of this ladder holds a repeated placement; the whole ladder was handed back unmoved */
+
+typedef struct mcq_temper3d {
+    int32_t N;             /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D (mcq_temper3d_device: as far as a ladder fits the LDS, see above) */
+    int32_t n_queens;      /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;      /* 1 .. 2^31 - 1, a multiple of replicas */
+    int64_t n_sweeps;      /* >= 0 */
+    int64_t first_sweep;   /* >= 0: global index of the call's sweep 0; (first_sweep + n_sweeps) Q < 2^62 */
+    int64_t replicas;      /* R: 2, 4, 8 or 16 */
+    int64_t exchange_every; /* K >= 1 */
+    int64_t n_events;      /* floor((first_sweep + n_sweeps) / K) - floor(first_sweep / K): the rows of swap_table */
+    const uint32_t* seeds; /* [n_chains] */
+    const uint32_t* table; /* [n_sweeps][R][table_len]: T; may be NULL when n_sweeps = 0 */
+    int64_t table_len;     /* D, 1 .. MCQ_MAX_HEATBATH_TABLE */
+    const uint32_t* swap_table; /* [n_events][R - 1][swap_len]: X; may be NULL when n_events = 0 */
+    int64_t swap_len;      /* DX, 1 .. MCQ_MAX_TEMPER_SWAP_TABLE */
+    const uint8_t* rung_in; /* optional [n_chains]: a permutation of 0 .. R - 1 per ladder; NULL = slot r on rung r mod R */
+    uint8_t* rung_out;     /* optional [n_chains] */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;    /* [n_chains][Q][3]; may be state_in */
+    int32_t* energy_in;    /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;   /* optional [n_chains] */
+    int32_t* best_energy;  /* optional [n_chains] */
+    int64_t* best_sweep;   /* optional [n_chains] */
+    uint8_t* best_state;   /* optional [n_chains][Q][3]; neither state_in nor state_out */
+    int64_t* n_changed;    /* optional [n_chains] */
+    int32_t* energy_hist;  /* optional [n_chains][hist_stride] */
+    int64_t hist_stride;   /* entries per chain row of energy_hist and of rung_hist, >= n_sweeps + 1 (read only when one of them is given) */
+    int64_t* n_exchanges;  /* optional [n_chains] */
+    uint8_t* rung_hist;    /* optional [n_chains][hist_stride] */
+    int64_t* pair_accepted; /* optional [n_chains / R][R - 1] */
+    int32_t* flags;        /* optional [n_chains]: MCQ_HEATBATH3D_REPEATED | MCQ_TEMPER3D_HELD */
+} mcq_temper3d;
+
+/* the message of the last error of the calling thread from the two mcq_temper3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_temper3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  ONE kernel enqueued on `hip_stream`, a workgroup per ladder, the exchange through LDS and
+ * two barriers; asynchronous: nothing is copied back and nothing synchronises.  MCQ_EINVAL before any launch and without touching a
+ * device: what mcq_heatbath3d_device and mcq_temper_device refuse of the fields they share with this block, and any (N, R, Q, table_len)
+ * whose ladder exceeds MCQ_MAX_TEMPER_LDS (the message names N, R, Q and the bytes) or whose lanes would add more than 255 weights in
+ * 32 bits.  NOT checked, being on the device: what mcq_heatbath3d_device does not check of T, and rung_in -- a rung is clamped to
+ * R - 1, and a ladder whose rungs are no permutation gets outputs that are not the rule's; nothing leaves the arrays. */
+int mcq_temper3d_device(const mcq_temper3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, for every N up to MCQ_MAX_N_QUENCH3D and every R (no LDS here); needs no GPU.
+ * Equal to the kernel bit for bit on every output.  It reads its inputs, so it also refuses with MCQ_EINVAL an entry of T above
+ * 2^MCQ_HEATBATH_WEIGHT_BITS and a rung_in that is no permutation of 0 .. R - 1 in some ladder; the message names the place. */
+int mcq_temper3d_host(const mcq_temper3d* q);
 
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 

@@ -207,6 +207,11 @@ def lib():
         L.mcq_temper_device.argtypes = [C.POINTER(abi.Temper), C.c_void_p]
         L.mcq_temper_host.restype = C.c_int
         L.mcq_temper_host.argtypes = [C.POINTER(abi.Temper)]
+        L.mcq_temper3d_last_error.restype = C.c_char_p
+        L.mcq_temper3d_device.restype = C.c_int
+        L.mcq_temper3d_device.argtypes = [C.POINTER(abi.Temper3D), C.c_void_p]
+        L.mcq_temper3d_host.restype = C.c_int
+        L.mcq_temper3d_host.argtypes = [C.POINTER(abi.Temper3D)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -350,6 +355,28 @@ def temper_host(q):
 def temper_device(q, stream):
     """mcq_temper_device on a filled abi.Temper block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_temper(lib().mcq_temper_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_temper3d(rc):
+    """_check for the mcq_temper3d_* calls, which keep their own message (mcq_temper3d_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_temper3d_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def temper3d_host(q):
+    """mcq_temper3d_host on a filled abi.Temper3D block of HOST pointers.  Pure host code, no GPU."""
+    _check_temper3d(lib().mcq_temper3d_host(C.byref(q)))
+
+
+def temper3d_device(q, stream):
+    """mcq_temper3d_device on a filled abi.Temper3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_temper3d(lib().mcq_temper3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def resample_plan_host(energies, population, table, offsets):

@@ -315,6 +315,29 @@ class Temper(C.Structure):
 TEMPER_DTYPES = dict(HEATBATH_DTYPES, rung_out=np.uint8, n_exchanges=np.int64)
 
 
+TEMPER3D_HELD = 2              # include/mcq.h: MCQ_TEMPER3D_HELD: bit 1 of flags
+TEMPER3D_STATIC_LDS = 256      # MCQ_TEMPER3D_STATIC_LDS
+
+
+class Temper3D(C.Structure):
+    """include/mcq.h: mcq_temper3d -- parallel tempering of full_3d heat-bath queen sweeps, one ladder per workgroup"""
+    _fields_ = [("n_queens", t) if f == "mode" else (f, t) for f, t in Temper._fields_] + [("flags", C.c_void_p)]
+
+
+# the per-chain outputs of a tempered full_3d call besides the placements
+TEMPER3D_DTYPES = dict(TEMPER_DTYPES, flags=np.int32)
+
+
+def temper3d_lds_bytes(N, R, Q=None, table_len=MAX_HEATBATH_TABLE):
+    """The bytes of LDS a ladder of mcq_temper3d_device takes (include/mcq.h, below the rule): it runs what stays within
+    MAX_TEMPER_LDS - TEMPER3D_STATIC_LDS."""
+    N, R = int(N), int(R)
+    Q = N * N if Q is None or int(Q) == 0 else int(Q)
+    cells, cpd = N ** 3, 4 if N <= 19 else 2
+    chain = (72 + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2 + 3) // 4 * 4
+    return 4 * (R * chain + R * int(table_len) + 3 * R)
+
+
 def temper_events(first_sweep, n_sweeps, exchange_every):
     """The exchange events of a call (include/mcq.h, tempering rule, item 3): floor((first_sweep + n_sweeps) / K) - floor(first_sweep / K)."""
     K = int(exchange_every)
