@@ -879,6 +879,62 @@ int mcq_temper3d_device(const mcq_temper3d* q, void* hip_stream);
  * 2^MCQ_HEATBATH_WEIGHT_BITS and a rung_in that is no permutation of 0 .. R - 1 in some ladder; the message names the place. */
 int mcq_temper3d_host(const mcq_temper3d* q);
 
+/*
+ * Pair-move quench: the deterministic descent of board placements to a minimum under single-height moves AND under moves of two
+ * columns at once (csrc/mcq_quench_pairs.hip) -- NOT a mode of the reference; never a default, like Philox, replica exchange,
+ * population annealing, the quenches, the heat baths and the tempered sweeps.  mcq_quench above certifies a placement against the
+ * single-move neighbourhood; this block tests it against the smallest larger one and descends below it.  Boards only.  The rule is
+ * integer-exact:
+ *   1. every input byte is clamped to N - 1 first; a(c, k) and E are those of the mcq_quench rule, items 1 - 2.  Two columns
+ *      c = (i, j) != c' = (i', j') are ALIGNED when di = 0 or dj = 0 or |di| = |dj| (they share a row, a column or a diagonal of the
+ *      board).  att((c, k), (c', k')) = 1 when the columns are aligned and |k - k'| = 0 or d, d = max(|di|, |dj|); otherwise 0.
+ *   2. DESCENT: passes of the mcq_quench rule, items 3 - 4, until a pass moves nothing; there is no pass limit.  n_moves counts the
+ *      single moves of all descents of the run.  energy_single is E after the FIRST descent: what mcq_quench returns with
+ *      max_passes = 0.
+ *   3. SCAN: the candidates are (c1, c2, k1, k2) with c1 < c2 (row-major indices), the two columns aligned, k1 != h(c1) and
+ *      k2 != h(c2).  With h1 = h(c1), h2 = h(c2):
+ *        D = a(c1, k1) - a(c1, h1) + a(c2, k2) - a(c2, h2)
+ *            - att((c1, k1), (c2, h2)) - att((c1, h1), (c2, k2)) + att((c1, h1), (c2, h2)) + att((c1, k1), (c2, k2))
+ *      which is the change of E when both heights change at once.  The scan takes the candidate with the lexicographically smallest
+ *      (D, c1, c2, k1, k2).  n_rounds counts the scans.
+ *   4. if that D >= 0 the run ends with certified = 1: no single move and no pair move lowers E.  (A pair of columns that are not
+ *      aligned has D = the sum of two single-move differences, which are >= 0 behind a descent: it cannot improve, which is why the
+ *      candidates are the aligned pairs.)  Otherwise both heights are applied, E += D, n_pair_moves grows by 1, and the run goes back
+ *      to item 2.  When max_rounds > 0 and n_rounds has reached it after an applied move, one more descent runs and the run ends
+ *      with certified = 0.  Every pair move lowers E by at least 1, so a run ends within energy_in + 1 rounds; a 2-move minimum comes
+ *      back with n_pair_moves = 0, n_rounds = 1, certified = 1.
+ * An implementation may skip candidates that cannot have D < 0 -- behind a descent both single-move differences are >= 0 and the four
+ * att terms add at least -2, so D < 0 needs them to sum to at most 1 --; it may not change the result.
+ * N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS on the device and in host code alike: every a(c, k) is at most 4 (N - 1) = 124 there and
+ * fits a byte.  Chains do not interact, so state_out may be state_in.
+ */
+#define MCQ_MAX_N_QUENCH_PAIRS 32
+typedef struct mcq_quench_pairs {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS */
+    int32_t mode;           /* MCQ_MODE_BOARD; anything else is MCQ_EINVAL */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t max_rounds;     /* >= 0; 0 = until a scan finds no improving pair */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;     /* [n_chains][N*N]; may be state_in */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_single; /* optional [n_chains]: E after the first descent */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* n_moves;       /* optional [n_chains]: single moves of all descents */
+    int32_t* n_pair_moves;  /* optional [n_chains] */
+    int32_t* n_rounds;      /* optional [n_chains]: scans */
+    int32_t* certified;     /* optional [n_chains]: 1 = the last scan found no improving pair, 0 = max_rounds ended the run */
+    uint16_t* conflicts;    /* optional [n_chains][N*N]: a(c, h(c)) of the OUTPUT placement; its sum is 2 energy_out */
+} mcq_quench_pairs;
+
+/* the message of the last error of the calling thread from the two mcq_quench_pairs_* calls below (they do not set mcq_last_error()) */
+const char* mcq_quench_pairs_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`; asynchronous: nothing is copied back and nothing
+ * synchronises.  MCQ_EINVAL before any launch: mode other than board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative
+ * max_rounds, a NULL state_in or state_out. */
+int mcq_quench_pairs_device(const mcq_quench_pairs* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+int mcq_quench_pairs_host(const mcq_quench_pairs* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -212,6 +212,11 @@ def lib():
         L.mcq_temper3d_device.argtypes = [C.POINTER(abi.Temper3D), C.c_void_p]
         L.mcq_temper3d_host.restype = C.c_int
         L.mcq_temper3d_host.argtypes = [C.POINTER(abi.Temper3D)]
+        L.mcq_quench_pairs_last_error.restype = C.c_char_p
+        L.mcq_quench_pairs_device.restype = C.c_int
+        L.mcq_quench_pairs_device.argtypes = [C.POINTER(abi.QuenchPairs), C.c_void_p]
+        L.mcq_quench_pairs_host.restype = C.c_int
+        L.mcq_quench_pairs_host.argtypes = [C.POINTER(abi.QuenchPairs)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -289,6 +294,28 @@ def quench_host(q):
 def quench_device(q, stream):
     """mcq_quench_device on a filled abi.Quench block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_quench(lib().mcq_quench_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_quench_pairs(rc):
+    """_check for the mcq_quench_pairs_* calls, which keep their own message (mcq_quench_pairs_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_quench_pairs_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def quench_pairs_host(q):
+    """mcq_quench_pairs_host on a filled abi.QuenchPairs block of HOST pointers.  Pure host code, no GPU."""
+    _check_quench_pairs(lib().mcq_quench_pairs_host(C.byref(q)))
+
+
+def quench_pairs_device(q, stream):
+    """mcq_quench_pairs_device on a filled abi.QuenchPairs block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_quench_pairs(lib().mcq_quench_pairs_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def _check_quench3d(rc):

@@ -164,6 +164,34 @@ class Quench(C.Structure):
 QUENCH_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.int32, "n_passes": np.int32, "conflicts": np.uint16}
 
 
+MAX_N_QUENCH_PAIRS = 32        # include/mcq.h: MCQ_MAX_N_QUENCH_PAIRS
+
+
+class QuenchPairs(C.Structure):
+    """include/mcq.h: mcq_quench_pairs -- the descent of board placements under single-height moves and moves of two aligned columns"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("max_rounds", C.c_int64),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_single", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_pair_moves", C.c_void_p),
+        ("n_rounds", C.c_void_p),
+        ("certified", C.c_void_p),
+        ("conflicts", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a pair-move quench besides the placements: field -> dtype ("conflicts" has a row of N*N per chain)
+QUENCH_PAIRS_DTYPES = {"energy_in": np.int32, "energy_single": np.int32, "energy_out": np.int32, "n_moves": np.int32, "n_pair_moves": np.int32,
+                       "n_rounds": np.int32, "certified": np.int32, "conflicts": np.uint16}
+
+
 MAX_N_QUENCH3D = 32            # include/mcq.h: MCQ_MAX_N_QUENCH3D
 QUENCH3D_REPEATED = 1          # MCQ_QUENCH3D_REPEATED: bit 0 of flags
 

@@ -19,6 +19,8 @@ TEMPER_SOURCES = [os.path.join(CSRC, "mcq_temper.hip")]
 # parallel tempering of the full_3d heat-bath queen sweep, a ladder of attack fields per workgroup: a fourth list, as tests pin the
 # three above; compiled into the same library
 TEMPER3D_SOURCES = [os.path.join(CSRC, "mcq_temper3d.hip")]
+# the pair-move quench of board placements: a fifth list, as tests pin the four above; compiled into the same library
+PAIRS_SOURCES = [os.path.join(CSRC, "mcq_quench_pairs.hip")]
 # what the sources include: the C-ABI; the chain record of the sweep and the resume kernels; the attack field of the full_3d files;
 # what the four files outside the sweep (the quenches and the heat baths) share beyond it; the lane helpers of the board heat-bath column
 # update, which the tempered sweep shares
@@ -41,14 +43,14 @@ def stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    return any(os.path.getmtime(f) > t for f in SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + HEADERS)
+    return any(os.path.getmtime(f) > t for f in SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HEADERS)
 
 
 def build(force=False, verbose=False):
     """Compile the HIP kernels + C-ABI for gfx950; returns the path of the shared library."""
     if not force and not stale():
         return SO
-    cmd = [hipcc()] + FLAGS + ["-o", SO] + SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES
+    cmd = [hipcc()] + FLAGS + ["-o", SO] + SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)

@@ -258,13 +258,18 @@ def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.
     local minimum under single-height moves on the device (quench.py), and the board written is the one with the lowest QUENCHED energy
     over the runs (the first such run).  The call then returns FOUR values, (quenched energy, heights, path, info), with
     info = {"quenched": True, "run": r, "energy_before": that run's best_energy, "moves": the heights the quench changed}; the file
-    keeps the reference's format and has `_quenched` in its name.
+    keeps the reference's format and has `_quenched` in its name.  quench="pairs" (N <= 32) takes the pair-move quench instead
+    (quench.quench_pairs): the file has `_quenched_pairs` in its name and info is {"quenched": "pairs", "run", "energy_before", "moves",
+    "pair_moves", "certified"}.
 
     heatbath_sweeps (not in the reference; None = nothing changes): the board comes from that many heat-bath column sweeps per run
     (heatbath.anneal_heatbath) instead of n_steps Metropolis steps, beta_start -> beta_end over the sweeps, from the same initial
     placements; resample_every (then in sweeps), population, resample_seed and quench are honoured; `n_steps` and `runner` are unused.
     heatbath_form ("lines" or "counters", N <= 16) is anneal_heatbath's `form`: the kernel of the sweeps, not their result; unused
     without heatbath_sweeps."""
+    from . import quench as _quench
+
+    _quench.check_mode(quench, N)
     sp = {"type": "linear_annealing", "beta_start": beta_start, "beta_end": beta_end}
     if heatbath_sweeps is not None:
         from . import heatbath as _hb
@@ -295,10 +300,19 @@ def _write_competition(res, N, out_dir, timestamp, quench=False):
         if "quenched_state" not in res:  # independent chains: their best placements go through the quench here
             from . import quench as _quench
 
-            q = _quench.quench_states(N, np.asarray(res["best_state"]), conflicts=False)
+            if quench == "pairs":
+                q = _quench.quench_pairs(N, np.asarray(res["best_state"]), conflicts=False)
+                res = dict(res, quench_pair_moves=q["n_pair_moves"], quench_certified=q["certified"])
+            else:
+                q = _quench.quench_states(N, np.asarray(res["best_state"]), conflicts=False)
             res = dict(res, quenched_state=q["state"], quenched_energy=q["energy_out"], quench_moves=q["n_moves"])
         r = int(np.argmin(res["quenched_energy"]))
         heights = np.asarray(res["quenched_state"][r]).reshape(N, N)
+        if quench == "pairs":
+            path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}_quenched_pairs.txt"))
+            info = {"quenched": "pairs", "run": r, "energy_before": int(res["best_energy"][r]), "moves": int(res["quench_moves"][r]),
+                    "pair_moves": int(res["quench_pair_moves"][r]), "certified": bool(res["quench_certified"][r])}
+            return int(res["quenched_energy"][r]), heights, path, info
         path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}_quenched.txt"))
         info = {"quenched": True, "run": r, "energy_before": int(res["best_energy"][r]), "moves": int(res["quench_moves"][r])}
         return int(res["quenched_energy"][r]), heights, path, info

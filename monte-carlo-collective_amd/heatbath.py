@@ -269,7 +269,9 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     final_state / final_energy, initial_energy, best_state / best_energy / best_sweep (in whole-run sweeps; a later segment moves them
     only by a strictly lower energy), n_changed, `energy_hist` int32[n_chains][n_sweeps + 1] with trace=True (segments joined by dropping
     each later segment's entry 0, as anneal_population does), and with quench=True `quenched_state`, `quenched_energy`, `quench_moves`
-    (best_state through quench.quench_device on the same stream).
+    (best_state through quench.quench_device on the same stream).  quench="pairs" (boards up to N = 32) sends best_state through
+    quench.quench_pairs_device instead, the pair-move quench: the same three fields, and `quench_pair_moves`, `quench_rounds`,
+    `quench_certified`, `quench_energy_single` (what quench=True would have reached).
 
     mcmc_type="full_3d" (default "board": everything above) runs heat-bath QUEEN sweeps of Q queens in the cube (Q=None: N^2) through
     heatbath_queens_device: the placements are uint8[n_chains][3 Q], the start placements those of start_chains(..., mcmc_type="full_3d")
@@ -290,6 +292,9 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     import torch
 
     from . import population as _pop
+    from . import quench as _quench
+
+    _quench.check_mode(quench, N, board=mcmc_type != "full_3d")
 
     n_sweeps = int(n_sweeps)
     if n_sweeps < 0:
@@ -394,12 +399,10 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
             state = final
             e0, e1 = seg_e0[0], seg_e1[K - 1]
         if quench:  # behind the last fold, which has written acc["best_state"]; same stream, nothing waited for
-            from . import quench as _quench
-
             if cube:
                 quenched = _quench.quench_queens_device(N, acc["best_state"], Q=Qn, conflicts=False, stream=st)
             else:
-                quenched = _quench.quench_device(N, acc["best_state"], conflicts=False, stream=st)
+                quenched = _quench.hook_device(N, acc["best_state"], quench, st)
         st.synchronize()
 
     res = {"initial_energy": e0.cpu().numpy(), "final_energy": e1.cpu().numpy(), "final_state": state.cpu().numpy(),
@@ -410,8 +413,7 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     if trace:
         res["energy_hist"] = hist.cpu().numpy()
     if quenched is not None:
-        res["quenched_state"], res["quenched_energy"] = quenched["state"].cpu().numpy(), quenched["energy_out"].cpu().numpy()
-        res["quench_moves"] = quenched["n_moves"].cpu().numpy()
+        _quench.hook_results(res, quenched)
     if b is None:
         return res
     par = parents[: K - 1].cpu().numpy()

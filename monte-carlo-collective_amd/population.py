@@ -102,7 +102,9 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
     `timings` (a dict, optional) receives wall seconds of the enqueue + wait.
     quench=True (boards only; off by default, and nothing changes when off): best_state of every slot is quenched to a local minimum
     (quench.quench_device) on the same stream behind the last fold, with no host synchronisation before it; `res` gains `quenched_state`
-    uint8[n_chains][N*N], `quenched_energy` and `quench_moves` int32[n_chains].  Every other field is what the run without it returns."""
+    uint8[n_chains][N*N], `quenched_energy` and `quench_moves` int32[n_chains].  Every other field is what the run without it returns.
+    quench="pairs" (boards up to N = 32) takes the pair-move quench instead (quench.quench_pairs_device): the same three fields, and
+    `quench_pair_moves`, `quench_rounds`, `quench_certified`, `quench_energy_single` int32[n_chains]."""
     import time
 
     import torch
@@ -113,6 +115,9 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
     seeds = seeds.astype(np.uint32)
     if isinstance(schedule_params, (list, tuple)):
         raise ValueError("population annealing runs one schedule: schedule sets are not resampled")
+    from . import quench as _quench
+
+    _quench.check_mode(quench, N, board=abi.mode_of(mcmc_type) == abi.MODE_BOARD)
     if quench and abi.mode_of(mcmc_type) != abi.MODE_BOARD:
         raise ValueError("quench=True: the quench runs boards only (mcmc_type='board')")
     n = len(seeds)
@@ -194,9 +199,7 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
             done += L
         quenched = None
         if quench:  # behind the last fold, which has written acc["best_state"]; same stream, nothing waited for
-            from . import quench as _quench
-
-            quenched = _quench.quench_device(N, acc["best_state"], conflicts=False, stream=st)
+            quenched = _quench.hook_device(N, acc["best_state"], quench, st)
         t_wait = time.perf_counter()
         st.synchronize()
         t_end = time.perf_counter()
@@ -220,8 +223,7 @@ def anneal_population(N, n_steps, init_mode, schedule_params, seeds, resample_ev
     if states:
         res["best_state"], res["final_state"] = acc["best_state"].cpu().numpy(), last["final_state"]
     if quenched is not None:
-        res["quenched_state"], res["quenched_energy"] = quenched["state"].cpu().numpy(), quenched["energy_out"].cpu().numpy()
-        res["quench_moves"] = quenched["n_moves"].cpu().numpy()
+        _quench.hook_results(res, quenched)
     if reduced is not None:
         res.update({key: big.cpu().numpy() for key, big in reduced.items()})
     if hist is not None:

@@ -7,6 +7,10 @@ competition board) is whatever a thermal chain last held; the quench says whethe
 single-height moves, what the minimum below it is, recounts its energy on the device independently of the sweep, and returns the
 per-column conflict map.  Boards: N = 2 .. 128 (quench_states*, quench_device).
 
+quench_pairs, quench_pairs_device and quench_pairs_host go one neighbourhood further (include/mcq.h: mcq_quench_pairs;
+csrc/mcq_quench_pairs.hip): the descent also takes moves of two aligned columns at once and ends on a placement that no single move
+and no pair move lowers.  Boards, N = 2 .. 32; opt-in like everything here.
+
 full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_quench3d; csrc/mcq_quench3d.hip), N = 2 .. 32 and
 2 <= Q <= N^3 - 1: quench_queens, quench_queens_device, quench_queens_host.  The same labels apply -- the reference ships
 conflicts_for_queen (mcmc.py:185-226) and never calls it.
@@ -160,6 +164,92 @@ def to_numpy(res):
     if "conflicts" in out:
         out["conflicts"] = out["conflicts"].view(np.uint16)
     return out
+
+
+FIELDS_PAIRS = ("state", "energy_in", "energy_single", "energy_out", "n_moves", "n_pair_moves", "n_rounds", "certified", "conflicts")
+
+
+def _block_pairs(N, n, max_rounds):
+    q = abi.QuenchPairs()
+    q.N, q.mode, q.n_chains, q.max_rounds = int(N), abi.MODE_BOARD, int(n), int(max_rounds)
+    return q
+
+
+def quench_pairs_host(N, states, max_rounds=0, conflicts=True):
+    """mcq_quench_pairs_host: the pair-move rule in the library's plain host code, NumPy in and out, no GPU.  Same result as
+    quench_pairs."""
+    s = _host_states(N, states)
+    q = _block_pairs(N, s.shape[0], max_rounds)
+    out = _host_outputs(q, s, abi.QUENCH_PAIRS_DTYPES, {"conflicts": s.shape}, () if conflicts else ("conflicts",))
+    _lib.quench_pairs_host(q)
+    return out
+
+
+def quench_pairs_device(N, states, max_rounds=0, out=None, conflicts=True, stream=None):
+    """mcq_quench_pairs_device on a torch uint8 tensor [n_chains][N*N] of the current device (e.g. DeviceRun.t["best_state"]), enqueued
+    on `stream` (default: torch's current stream).  Asynchronous like quench_device: nothing is copied back and nothing synchronises.
+    `out` (optional) is the tensor the placements go to; it may be `states` itself (in place), default a new one.  Returns a dict of
+    tensors: `state` uint8 like `states`; `energy_in`, `energy_single` (E after the first single-move descent: quench_device's
+    energy_out), `energy_out`, `n_moves` (single moves of all descents), `n_pair_moves`, `n_rounds` (scans), `certified` int32[n_chains];
+    and, unless conflicts=False, `conflicts` int16[n_chains][N*N]."""
+    import torch
+
+    n = _device_states("quench_pairs_device", N, states)
+    dev = states.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = _block_pairs(N, n, max_rounds)
+        res = _device_outputs(q, states, out, abi.QUENCH_PAIRS_DTYPES, tuple(states.shape) if conflicts else None)
+        _lib.quench_pairs_device(q, st)
+    return res
+
+
+def quench_pairs(N, states, max_rounds=0, conflicts=True):
+    """The pair-move quench of board placements on the GPU: `states` is uint8[n_chains][N*N] (one board of N*N heights is taken as one
+    chain), bytes >= N are clamped to N - 1.  The placements descend under single-height moves, then take the best move of two aligned
+    columns at once, and so on until a scan finds no improving pair (certified = 1) or, with max_rounds > 0, that many scans have each
+    applied a move (certified = 0; the output is still a single-move minimum).  Returns a dict of NumPy arrays with the fields of
+    FIELDS_PAIRS; a placement with n_pair_moves == 0 and n_moves == 0 was a 2-move minimum already.  ValueError for what the library
+    refuses (N outside 2 .. 32, no chain, a negative max_rounds)."""
+    import torch
+
+    s = _host_states(N, states)
+    if s.shape[0] == 0:
+        _lib.quench_pairs_host(_block_pairs(N, 0, max_rounds))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = quench_pairs_device(N, torch.from_numpy(s).to(dev), max_rounds=max_rounds, conflicts=conflicts)
+    torch.cuda.current_stream(dev).synchronize()
+    return to_numpy(res)
+
+
+def check_mode(quench, N, board=True):
+    """ValueError for a `quench` the annealing hooks do not take: the one string they know is "pairs", which runs boards up to
+    N = abi.MAX_N_QUENCH_PAIRS only.  Anything else is read as a truth value, as before."""
+    if not isinstance(quench, str):
+        return
+    if quench != "pairs":
+        raise ValueError(f'quench must be False, True or "pairs", got {quench!r}')
+    if not board:
+        raise ValueError('quench="pairs": the pair-move quench runs boards only (mcmc_type="board")')
+    if not abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH_PAIRS:
+        raise ValueError(f'quench="pairs": N out of range [{abi.MIN_N}, {abi.MAX_N_QUENCH_PAIRS}]: {N}')
+
+
+def hook_device(N, best_state, quench, stream):
+    """What an annealing hook enqueues behind its last fold on a board's best_state: quench_device, or quench_pairs_device for "pairs"."""
+    if quench == "pairs":
+        return quench_pairs_device(N, best_state, conflicts=False, stream=stream)
+    return quench_device(N, best_state, conflicts=False, stream=stream)
+
+
+def hook_results(res, quenched):
+    """The hook's fields in a result dict: quenched_state, quenched_energy, quench_moves, and behind "pairs" also quench_pair_moves,
+    quench_rounds, quench_certified and quench_energy_single."""
+    res["quenched_state"], res["quenched_energy"] = quenched["state"].cpu().numpy(), quenched["energy_out"].cpu().numpy()
+    res["quench_moves"] = quenched["n_moves"].cpu().numpy()
+    if "n_pair_moves" in quenched:
+        res["quench_pair_moves"], res["quench_rounds"] = quenched["n_pair_moves"].cpu().numpy(), quenched["n_rounds"].cpu().numpy()
+        res["quench_certified"], res["quench_energy_single"] = quenched["certified"].cpu().numpy(), quenched["energy_single"].cpu().numpy()
 
 
 FIELDS_3D = ("state", "energy_in", "energy_out", "n_moves", "n_passes", "conflicts", "flags")

@@ -273,7 +273,9 @@ def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_
     Returns per chain final_state / final_energy, initial_energy, best_state / best_energy / best_sweep, n_changed, the ladder's
     figures -- final_rung, n_exchanges, pair_accepted, and ladder_statistics' pair_rate and exchanges_per_slot --, with trace=True
     energy_hist and rung_hist, and with quench=True quenched_state, quenched_energy, quench_moves (best_state through
-    quench.quench_device on the same stream).  ValueError before anything is launched for what temper_states refuses.
+    quench.quench_device on the same stream; quench="pairs", boards up to N = 32, takes quench.quench_pairs_device instead and adds
+    quench_pair_moves, quench_rounds, quench_certified, quench_energy_single).  ValueError before anything is launched for what
+    temper_states refuses.
 
     mcmc_type="full_3d" (default "board": everything above) runs tempered heat-bath QUEEN sweeps of Q queens in the cube (Q=None: N^2)
     through temper_queens_device: the placements are uint8[n_chains][3 Q], the start placements those of
@@ -281,6 +283,9 @@ def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_
     goes through quench.quench_queens_device."""
     import torch
 
+    from . import quench as _quench
+
+    _quench.check_mode(quench, N, board=mcmc_type != "full_3d")
     n_sweeps = int(n_sweeps)
     if n_sweeps < 0:
         raise ValueError(f"n_sweeps must be >= 0, got {n_sweeps}")
@@ -328,12 +333,10 @@ def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_
         else:
             seg = temper_device(N, state, seeds, beta, tables=tables, exchange_every=K, out=state, trace=trace, stream=st)
         if quench:
-            from . import quench as _quench
-
             if cube:
                 quenched = _quench.quench_queens_device(N, seg["best_state"], Q=Qn, conflicts=False, stream=st)
             else:
-                quenched = _quench.quench_device(N, seg["best_state"], conflicts=False, stream=st)
+                quenched = _quench.hook_device(N, seg["best_state"], quench, st)
         st.synchronize()
     got = to_numpy(seg)
     res = {"initial_energy": got["energy_in"], "final_energy": got["energy_out"], "final_state": got["state"], "best_energy": got["best_energy"],
@@ -346,6 +349,5 @@ def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_
     if trace:
         res["energy_hist"], res["rung_hist"] = got["energy_hist"], got["rung_hist"]
     if quenched is not None:
-        res["quenched_state"], res["quenched_energy"] = quenched["state"].cpu().numpy(), quenched["energy_out"].cpu().numpy()
-        res["quench_moves"] = quenched["n_moves"].cpu().numpy()
+        _quench.hook_results(res, quenched)
     return res
