@@ -710,7 +710,7 @@ int mcq_heatbath3d_host(const mcq_heatbath3d* q);
  *      (uint32 [n_sweeps][R][table_len]).  Unchanged means the same clamping, the same a(c, k), the same column order, the same word
  *      w = g N^2 + c of the Philox stream with key (seeds[slot], 1), the same U and selection, the same best values at sweep ends
  *      (before the sweep's event) and the same energy_hist.  A ladder whose R rows are equal is therefore R plain heat-bath chains,
- *      whatever the exchanges do.
+ *      whatever the exchanges do.  mcq_temper_counters_device below is a second way to obtain a(c, k), not a second rule.
  *   3. the exchange: exchange_every = K >= 1.  After the sweep with global index g an EVENT happens when (g + 1) mod K = 0; its global
  *      index is e = (g + 1) / K - 1.  The event looks at the pairs of neighbouring rungs (t, t + 1) with t = e (mod 2) and t + 1 < R.
  *      With a the slot on rung t, b the slot on rung t + 1 and Delta = E_b - E_a, the running energies after that sweep:
@@ -784,6 +784,16 @@ const char* mcq_temper_last_error(void);
  * rung_in -- a rung is clamped to R - 1, and a ladder whose rungs are no permutation gets outputs that are not the rule's; nothing
  * leaves the arrays. */
 int mcq_temper_device(const mcq_temper* q, void* hip_stream);
+/* The counter form of the same tempered sweep for N <= MCQ_MAX_N_TEMPER_COUNTERS: the same parameter block, the same asynchrony, the
+ * same refusals before any launch (through mcq_temper_last_error) and the same things NOT checked as mcq_temper_device, and MCQ_EINVAL
+ * before any launch for a larger N; the message names 16.  This is a second way to obtain a(c, k) -- the per-line queen counters of
+ * mcq_heatbath_counters_device above, one region per slot in the LDS of the ladder's workgroup -- and there is one rule: the outputs
+ * equal those of mcq_temper_device and of mcq_temper_host bit for bit.  A slot's counters stay with the slot at an exchange; only the
+ * rung moves.  LDS per ladder: R regions of 1 856, 4 288 or 7 616 bytes (N up to 8, 12, 16), 4 R table_len bytes of staged rows and
+ * 12 R bytes for the event, two ladders per workgroup at R = 2: at most 154 816 bytes (N = 16, R = 16, table_len = 512), so every
+ * block with N <= 16 that passes the checks fits MCQ_MAX_TEMPER_LDS. */
+#define MCQ_MAX_N_TEMPER_COUNTERS 16
+int mcq_temper_counters_device(const mcq_temper* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, for every N up to MCQ_MAX_N_BOARD (no LDS here); needs no GPU.  Equal to the
  * kernel bit for bit on every output.  It reads its inputs, so it also refuses with MCQ_EINVAL an entry of T above
  * 2^MCQ_HEATBATH_WEIGHT_BITS and a rung_in that is no permutation of 0 .. R - 1 in some ladder; the message names the place. */

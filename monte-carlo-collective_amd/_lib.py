@@ -205,6 +205,8 @@ def lib():
         L.mcq_temper_last_error.restype = C.c_char_p
         L.mcq_temper_device.restype = C.c_int
         L.mcq_temper_device.argtypes = [C.POINTER(abi.Temper), C.c_void_p]
+        L.mcq_temper_counters_device.restype = C.c_int
+        L.mcq_temper_counters_device.argtypes = [C.POINTER(abi.Temper), C.c_void_p]
         L.mcq_temper_host.restype = C.c_int
         L.mcq_temper_host.argtypes = [C.POINTER(abi.Temper)]
         L.mcq_temper3d_last_error.restype = C.c_char_p
@@ -382,6 +384,12 @@ def temper_host(q):
 def temper_device(q, stream):
     """mcq_temper_device on a filled abi.Temper block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_temper(lib().mcq_temper_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def temper_counters_device(q, stream):
+    """mcq_temper_counters_device (the counter form, N <= abi.MAX_N_TEMPER_COUNTERS) on a filled abi.Temper block of DEVICE pointers,
+    enqueued on the torch stream `stream`; asynchronous."""
+    _check_temper(lib().mcq_temper_counters_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def _check_temper3d(rc):

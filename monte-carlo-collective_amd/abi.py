@@ -303,6 +303,7 @@ HEATBATH3D_DTYPES = dict(HEATBATH_DTYPES, flags=np.int32)
 MAX_TEMPER_SWAP_TABLE = 4096   # include/mcq.h: MCQ_MAX_TEMPER_SWAP_TABLE
 MAX_TEMPER_LDS = 160 * 1024    # MCQ_MAX_TEMPER_LDS
 TEMPER_REPLICAS = (2, 4, 8, 16)
+MAX_N_TEMPER_COUNTERS = 16     # MCQ_MAX_N_TEMPER_COUNTERS: the largest N of mcq_temper_counters_device
 
 
 class Temper(C.Structure):
@@ -364,6 +365,19 @@ def temper3d_lds_bytes(N, R, Q=None, table_len=MAX_HEATBATH_TABLE):
     cells, cpd = N ** 3, 4 if N <= 19 else 2
     chain = (72 + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2 + 3) // 4 * 4
     return 4 * (R * chain + R * int(table_len) + 3 * R)
+
+
+def temper_counters_lds_bytes(N, R, table_len=MAX_HEATBATH_TABLE):
+    """The bytes of LDS a workgroup of mcq_temper_counters_device takes (N <= MAX_N_TEMPER_COUNTERS), the arithmetic of its launch: per
+    ladder R chain regions of the counter form -- (6 NP - 2)(5 NP - 2) counters and NP^2 heights, NP = N rounded up to 8, 12 or 16,
+    rounded to 64 bytes off a multiple of 128: 1 856, 4 288 or 7 616 --, 4 R table_len bytes of staged rows and 12 R bytes for the
+    event; two ladders where R = 2 (one is half a wavefront).  Never above MAX_TEMPER_LDS."""
+    N, R = int(N), int(R)
+    if not MIN_N <= N <= MAX_N_TEMPER_COUNTERS or R not in TEMPER_REPLICAS:
+        raise ValueError(f"the counter form of the tempered sweep runs N = {MIN_N} .. {MAX_N_TEMPER_COUNTERS} with 2, 4, 8 or 16 replicas, got N = {N}, R = {R}")
+    NP = 8 if N <= 8 else 12 if N <= 12 else 16
+    chain = ((6 * NP - 2) * (5 * NP - 2) + NP * NP + 63) // 128 * 128 + 64
+    return (2 if R == 2 else 1) * (R * chain + 4 * R * int(table_len) + 12 * R)
 
 
 def temper_events(first_sweep, n_sweeps, exchange_every):

@@ -1,7 +1,9 @@
 // mcq_columns.h -- the lane helpers of the board heat-bath column update, shared by csrc/mcq_heatbath.hip and csrc/mcq_temper.hip: the
 // lanes of a GROUP (16, 32 or 64 of a wavefront) are the candidate heights of one column.  DPP row rotations and shifts for the
 // minimum and the prefix sum over a group, and the test of one line of LDS cells against a lane's heights.  Moved here as they stood
-// in mcq_heatbath.hip; the device code of that file's kernels is what it was (profiles/tempering_refactor.md).
+// in mcq_heatbath.hip; the device code of that file's kernels is what it was (profiles/tempering_refactor.md).  The layout of the counter
+// form's chain region (counter_offset and its two sizes) stands here for the same reason: both counter kernels read it from one place
+// (profiles/tempering_counters.md).
 #ifndef MCQ_COLUMNS_H
 #define MCQ_COLUMNS_H
 
@@ -74,6 +76,23 @@ __device__ __forceinline__ void line_hits(const uint32_t* line, int pos, int k0,
         }
     }
 }
+
+// ---- the counter form (N <= 16): where a chain keeps the queen counts of the cube's 12 line families, one byte per line ----
+// A counter is at
+//   line (5N - 2) + v,   line = i | N + j | 3N - 1 + i - j | 4N - 1 + i + j   (6N - 2 lines in the plane),
+//                        v = k | 2N - 1 - pos + k | 3N - 1 + pos + k          (height step 0, +1, -1; pos = j along a row, i otherwise),
+// so the lanes of a group, the heights k, read 16 consecutive bytes per family.  counter_offset is the address at k = 0.
+__device__ __forceinline__ int counter_offset(int dir, int step, int i, int j, int N) {
+    const int line = dir == 0 ? i : dir == 1 ? N + j : dir == 2 ? 3 * N - 1 + i - j : 4 * N - 1 + i + j;
+    const int pos = dir == 0 ? j : i;
+    const int v = step == 0 ? 0 : step == 1 ? 2 * N - 1 - pos : 3 * N - 1 + pos;
+    return line * (5 * N - 2) + v;
+}
+
+// bytes of a chain's counters at the padding NP (8, 12 or 16: a multiple of 4), and of its whole region -- the counters and ONE copy of
+// the heights, 64 bytes off a multiple of 128, so that the two chains of a half-wavefront read different banks: 1 856, 4 288, 7 616
+__host__ __device__ constexpr int counter_bytes(int NP) { return (6 * NP - 2) * (5 * NP - 2); }
+__host__ __device__ constexpr int counter_region_bytes(int NP) { return (counter_bytes(NP) + NP * NP + 63) / 128 * 128 + 64; }
 
 }  // namespace mcq_columns
 

@@ -28,6 +28,7 @@
 
 namespace {
 
+using mcq_columns::counter_offset;
 using mcq_columns::group_min;
 using mcq_columns::group_scan;
 using mcq_columns::line_hits;
@@ -191,28 +192,19 @@ __global__ __launch_bounds__(64) void mcq_heatbath_kernel(HeatbathArgs a) {
 // The same walk with the cells of a column never looked at.  The 12 line families of the cube that matter -- in-plane direction (0,1),
 // (1,0), (1,1), (1,-1), height step 0, +1, -1 per cell along the line -- keep one byte each per line: the number of queens on it.
 //   a(c, k) = the sum over the 12 families of the counter of the line through (i, j, k)  -  12 [k = h(c)]
-// (the column's own queen lies on all 12 lines through its cell and on none through another cell of its column).  A counter is at
-//   line (5N - 2) + v,   line = i | N + j | 3N - 1 + i - j | 4N - 1 + i + j   (6N - 2 lines in the plane),
-//                        v = k | 2N - 1 - pos + k | 3N - 1 + pos + k          (height step 0, +1, -1; pos = j along a row, i otherwise),
-// so the lanes of a group, the heights k, read 16 consecutive bytes per family.  A chain's region holds these (6N - 2)(5N - 2) bytes
-// and ONE copy of the heights; regions are 64 bytes off a multiple of 128, so that the two chains of a half-wavefront read different
-// banks.  The counters are built once from the clamped input with 32-bit LDS atomics of 1 << 8 (byte in the dword): bytes of one dword
-// belong to different lines, and a counter stays within 0 .. N <= 16, so a byte neither carries nor borrows.  A changed height moves 24
+// (the column's own queen lies on all 12 lines through its cell and on none through another cell of its column).  Where a counter is
+// (counter_offset) and how large a chain's region -- these (6N - 2)(5N - 2) bytes and ONE copy of the heights -- is stands in
+// csrc/mcq_columns.h, which csrc/mcq_temper.hip's counter kernel shares.  The counters are built once from the clamped input with 32-bit
+// LDS atomics of 1 << 8 (byte in the dword): bytes of one dword belong to different lines, and a counter stays within 0 .. N <= 16, so a
+// byte neither carries nor borrows.  A changed height moves 24
 // counters before the next column is visited: lane f < 12 of the group owns family f and issues one atomic subtraction on the line
 // through the old cell and one addition on the line through the new one.  The chains of a wavefront diverge on "changed"; there is no
 // barrier inside that branch, and the LDS serves the instructions of one wavefront in their order, so the next column's reads see them.
-__device__ __forceinline__ int counter_offset(int dir, int step, int i, int j, int N) {
-    const int line = dir == 0 ? i : dir == 1 ? N + j : dir == 2 ? 3 * N - 1 + i - j : 4 * N - 1 + i + j;
-    const int pos = dir == 0 ? j : i;
-    const int v = step == 0 ? 0 : step == 1 ? 2 * N - 1 - pos : 3 * N - 1 + pos;
-    return line * (5 * N - 2) + v;
-}
-
 template <int NP>
 __global__ __launch_bounds__(64) void mcq_heatbath_counters_kernel(HeatbathArgs a) {
     constexpr int GW = 16, CPW = 64 / GW;
-    constexpr int CNT = (6 * NP - 2) * (5 * NP - 2);                  // bytes of counters; a multiple of 4 for NP = 8, 12, 16
-    constexpr int CHAIN = (CNT + NP * NP + 63) / 128 * 128 + 64;       // bytes of a chain's region: >= CNT + NP^2, = 64 mod 128
+    constexpr int CNT = mcq_columns::counter_bytes(NP);                // bytes of counters; a multiple of 4 for NP = 8, 12, 16
+    constexpr int CHAIN = mcq_columns::counter_region_bytes(NP);       // bytes of a chain's region: >= CNT + NP^2, = 64 mod 128
     static_assert(CNT % 4 == 0 && NP <= GW, "counter layout");
     __shared__ __attribute__((aligned(16))) uint32_t lds[CPW * CHAIN / 4];
     __shared__ uint32_t tab[512];

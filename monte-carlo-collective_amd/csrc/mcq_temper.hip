@@ -15,6 +15,12 @@
 //           (X comes from global memory: an event is rare), writes the two new rungs and counts the accept in a register it keeps for
 //           the whole kernel; barrier; every chain reads its rung back.  Every barrier sits in control flow that is uniform over the
 //           workgroup: the sweep count is the launch's, and "is this sweep followed by an event" depends on g and K alone.
+//   counter form (N <= MCQ_MAX_N_TEMPER_COUNTERS, mcq_temper_counters_device): mcq_temper_counters_kernel is the same ladder with the
+//           column update of mcq_heatbath_counters_kernel -- per chain the byte counters of the cube's 12 line families and one copy of
+//           the heights (csrc/mcq_columns.h: counter_offset, counter_region_bytes), 12 byte reads per height, 24 LDS atomics where a
+//           drawn height differs.  16 lanes per chain for every N; instantiated per (padding, R) with the launch bounds of its real
+//           workgroup (64, 64, 128 or 256 lanes), which the 1 024 of the kernel above would cap at 128 VGPRs.  A slot's counters stay
+//           with the slot at an exchange: only the rung moves.
 //   host    mcq_temper_host: the same rule over host buffers, ladder by ladder.
 //
 // Built for gfx950 only, with csrc/mcq_hip.hip:  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
@@ -29,6 +35,7 @@
 
 namespace {
 
+using mcq_columns::counter_offset;
 using mcq_columns::group_min;
 using mcq_columns::group_scan;
 using mcq_columns::line_hits;
@@ -252,6 +259,168 @@ __global__ __launch_bounds__(1024) void mcq_temper_kernel(TemperArgs a) {
     if (a.pair_accepted && tl < R - 1) a.pair_accepted[lad * (R - 1) + tl] = accepted;
 }
 
+// ---- the counter form, N <= MCQ_MAX_N_TEMPER_COUNTERS (include/mcq.h: mcq_temper_counters_device) ----
+// The ladder of mcq_temper_kernel -- the R rows staged per sweep, the row of the slot's rung, the event's two barriers and three arrays,
+// pair_accepted in registers, the ladder beyond the last one -- around the column update of mcq_heatbath_counters_kernel
+// (csrc/mcq_heatbath.hip, where the counters are explained).  Dynamic LDS per ladder: the R counter regions, the R D dwords of rows and
+// 3 R words for the event.  A chain's region is touched by the 16 lanes of its group alone, which sit in one wavefront, so the update's
+// atomics need no barrier: the branch on "changed" holds none, and every barrier is where mcq_temper_kernel has it.
+template <int NP, int R>
+__global__ __launch_bounds__(temper_threads(R, 16)) void mcq_temper_counters_kernel(TemperArgs a) {
+    constexpr int GW = 16, LT = R * GW;                               // lanes of a chain, lanes of a ladder
+    constexpr int CNT = mcq_columns::counter_bytes(NP);               // bytes of counters; a multiple of 4 for NP = 8, 12, 16
+    constexpr int CHAIN = mcq_columns::counter_region_bytes(NP);      // bytes of a chain's region: >= CNT + NP^2, = 64 mod 128
+    static_assert(CNT % 4 == 0 && NP <= GW, "counter layout");
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int N = a.N, Q = N * N, D = a.table_len;
+    const int lane = threadIdx.x & (GW - 1);
+    const int wgrp = (threadIdx.x & 63) / GW;                // the group's place in its wavefront
+    const int lib = threadIdx.x / LT;                        // ladder in the workgroup (0, or 0 / 1 where two share it: R = 2)
+    const int tl = threadIdx.x - lib * LT;                   // lane of the ladder
+    const int slot = tl / GW;                                // chain of the ladder
+    const long long ladder = (long long)blockIdx.x * (temper_threads(R, GW) / LT) + lib;
+    const bool valid = ladder < a.n_ladders;
+    const long long lad = valid ? ladder : a.n_ladders - 1;  // a ladder beyond the last one walks the last ladder and writes nothing
+    const long long ch = lad * R + slot;
+    uint32_t* lbase = lds + lib * a.ladder_words;
+    uint32_t* cw = lbase + slot * (CHAIN / 4);
+    const uint8_t* cb = (const uint8_t*)cw;
+    uint8_t* hts = (uint8_t*)cw + CNT;
+    uint32_t* tab = lbase + R * (CHAIN / 4);                 // [R][D]: the sweep's rows by rung
+    int* e_by_rung = (int*)(tab + R * D);
+    int* slot_by_rung = e_by_rung + R;
+    int* rung_by_slot = slot_by_rung + R;
+    for (int w = lane; w < CNT / 4; w += GW) cw[w] = 0u;
+    int rung = a.rung_in ? min((int)a.rung_in[ch], R - 1) : slot;
+    if (tl < R) {  // (a rung_in that is no permutation leaves a rung without a slot: it keeps this one, and nothing leaves the arrays)
+        e_by_rung[tl] = 0;
+        slot_by_rung[tl] = tl;
+    }
+    if (lane == 0) rung_by_slot[slot] = rung;
+    __syncthreads();
+    const uint8_t* in = a.state_in + ch * Q;
+    for (int c = lane; c < Q; c += GW) {
+        const int v = in[c], i = c / N, j = c - i * N;
+        const int hv = v < N ? v : N - 1;
+        hts[c] = (uint8_t)hv;
+#pragma unroll
+        for (int f = 0; f < 12; f++) {
+            const int b = counter_offset(f / 3, f % 3, i, j, N) + hv;
+            atomicAdd(cw + (b >> 2), 1u << (8 * (b & 3)));
+        }
+    }
+    __syncthreads();
+    if (valid && a.best_state) {  // until a sweep end is strictly lower: the (clamped) input
+        uint8_t* out = a.best_state + ch * Q;
+        for (int c = lane; c < Q; c += GW) out[c] = hts[c];
+    }
+    const int k0 = lane, kr = min(lane, N - 1);  // a lane beyond N reads the counters of the last height and is left out below
+    const int own_dir = lane / 3, own_step = lane - 3 * own_dir;  // lane f < 12 updates family f
+    const uint32_t seed = a.seeds[ch], seed0 = a.seeds[lad * R];
+    int32_t* hist = a.energy_hist ? a.energy_hist + ch * a.hist_stride : nullptr;
+    uint8_t* rhist = a.rung_hist ? a.rung_hist + ch * a.hist_stride : nullptr;
+    if (valid && rhist && lane == 0) rhist[0] = (uint8_t)rung;
+
+    int E = 0, e_in = 0, best = 0;
+    long long best_sweep = 0, changed = 0, exchanges = 0, accepted = 0;  // accepted: of pair tl, in the lanes tl < R - 1 of a ladder
+    uint32_t rnd[4] = {0, 0, 0, 0};
+    // sweep -1 is the recount of the input: the same walk with no update
+    for (long long s = -1; s < a.n_sweeps; s++) {
+        const bool recount = s < 0;
+        if (!recount) {
+            __syncthreads();
+            const uint32_t* row = a.table + s * R * D;
+            for (int d = tl; d < R * D; d += LT) tab[d] = row[d];
+            __syncthreads();
+        }
+        const uint32_t* trow = tab + rung * D;
+        const unsigned long long w0 = recount ? 0ull : (unsigned long long)(a.first_sweep + s) * (unsigned long long)Q;
+        int twoE = 0;
+        for (int i = 0, c = 0; i < N; i++)
+            for (int j = 0; j < N; j++, c++) {
+                int c0 = 0;
+#pragma unroll
+                for (int f = 0; f < 12; f++) c0 += cb[counter_offset(f / 3, f % 3, i, j, N) + kr];
+                const int cur = hts[c];
+                c0 -= k0 == cur ? 12 : 0;
+                const int a_old = __shfl(c0, cur, GW);
+                if (recount) {
+                    twoE += a_old;
+                    continue;
+                }
+                const int a_min = group_min<GW>(k0 < N ? c0 : INT_MAX);
+                const uint32_t wt0 = k0 < N ? trow[min(c0 - a_min, D - 1)] : 0u;
+                uint32_t W;
+                const uint32_t C0 = group_scan<GW>(wt0, lane, W);
+                const unsigned long long w = w0 + (unsigned)c;
+                if ((w & 3) == 0 || c == 0) philox_block((uint32_t)(w >> 2), (uint32_t)(w >> 34), seed, 1u, rnd);
+                const int e = (int)(w & 3);
+                const uint32_t x = e == 0 ? rnd[0] : e == 1 ? rnd[1] : e == 2 ? rnd[2] : rnd[3];
+                const uint32_t U = __umulhi(x, W);
+                // the smallest k with C_k > U = the number of heights with C_k <= U (C is non-decreasing; a lane beyond N holds W > U)
+                int kn = __popcll((__ballot(C0 <= U) >> (wgrp * GW)) & ((1ull << GW) - 1));
+                kn = min(kn, N - 1);  // (only a table with T[0] = 0, W = 0, gets here: the last height, as in the host code)
+                const int a_new = __shfl(c0, kn, GW);
+                E += a_new - a_old;
+                changed += kn != cur;
+                if (kn != cur && lane < 12) {
+                    const int o = counter_offset(own_dir, own_step, i, j, N);
+                    const int b0 = o + cur, b1 = o + kn;
+                    atomicSub(cw + (b0 >> 2), 1u << (8 * (b0 & 3)));
+                    atomicAdd(cw + (b1 >> 2), 1u << (8 * (b1 & 3)));
+                }
+                hts[c] = (uint8_t)kn;  // by every lane of the group: same address, same value
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (no instruction: the compiler keeps the next column's reads behind the updates)
+            }
+        if (recount) {
+            E = e_in = best = twoE >> 1;
+            if (valid && hist && lane == 0) hist[0] = E;
+            continue;
+        }
+        if (valid && hist && lane == 0) hist[s + 1] = E;
+        if (E < best) {
+            best = E;
+            best_sweep = s + 1;
+            if (valid && a.best_state) {
+                uint8_t* out = a.best_state + ch * Q;
+                for (int c = lane; c < Q; c += GW) out[c] = hts[c];
+            }
+        }
+        const long long g1 = a.first_sweep + s + 1;
+        if (g1 % a.every == 0) {  // uniform over the launch: the two barriers are met by every lane of the workgroup
+            const long long ev = g1 / a.every - 1;
+            if (lane == 0) {
+                e_by_rung[rung] = E;
+                slot_by_rung[rung] = slot;
+            }
+            __syncthreads();
+            if (tl < R - 1 && ((tl ^ (int)ev) & 1) == 0) {
+                const int sa = slot_by_rung[tl], sb = slot_by_rung[tl + 1];
+                const uint32_t* X = a.swap_table + ((ev - a.events_before) * (R - 1) + tl) * (long long)a.swap_len;
+                if (pair_swaps(e_by_rung[tl + 1] - e_by_rung[tl], X, a.swap_len, seed0, (unsigned long long)ev * (unsigned)R + (unsigned)tl)) {
+                    rung_by_slot[sa] = tl + 1;
+                    rung_by_slot[sb] = tl;
+                    accepted++;
+                }
+            }
+            __syncthreads();
+            const int now = rung_by_slot[slot];
+            exchanges += now != rung;
+            rung = now;  // the slot keeps its counters: only the rung moves
+        }
+        if (valid && rhist && lane == 0) rhist[s + 1] = (uint8_t)rung;
+    }
+    if (!valid) return;
+    uint8_t* out = a.state_out + ch * Q;
+    for (int c = lane; c < Q; c += GW) out[c] = hts[c];
+    if (lane == 0) {
+        mcq_post::store_heatbath_figures(a, ch, e_in, E, best, best_sweep, changed);
+        if (a.rung_out) a.rung_out[ch] = (uint8_t)rung;
+        if (a.n_exchanges) a.n_exchanges[ch] = exchanges;
+    }
+    if (a.pair_accepted && tl < R - 1) a.pair_accepted[lad * (R - 1) + tl] = accepted;
+}
+
 // the padding of a board's lines and the lanes of a chain, as mcq_heatbath_device chooses them; 0 beyond N = 64 (two heights per lane
 // there: 96 KB of placements per chain, so that no ladder fits)
 int line_padding(int N) { return N <= 8 ? 8 : N <= 12 ? 12 : N <= 16 ? 16 : N <= 24 ? 24 : N <= 32 ? 32 : N <= 64 ? 64 : 128; }
@@ -262,6 +431,14 @@ long long ladder_words(int N, int R, int D) {
     const long long NP = line_padding(N);
     return (R * (6 * NP * NP / 4) + (long long)R * D + 3 * R + 3) / 4 * 4;
 }
+
+// the counter form: the padding of its chain region, and the dwords of LDS of one ladder -- R regions, the staged rows, the event
+int counters_padding(int N) { return N <= 8 ? 8 : N <= 12 ? 12 : 16; }
+long long counters_ladder_words(int N, int R, int D) {
+    return ((long long)R * mcq_columns::counter_region_bytes(counters_padding(N)) + 4ll * R * D + 12 * R) / 4;
+}
+// the largest workgroup of the counter form, N = 16 with 16 replicas and the longest table, stays within a workgroup's LDS: so does every other
+static_assert(16 * mcq_columns::counter_region_bytes(16) + 4 * 16 * MCQ_MAX_HEATBATH_TABLE + 12 * 16 <= MCQ_MAX_TEMPER_LDS, "counter ladder");
 
 long long events_of(long long first, long long n, long long K) { return (first + n) / K - first / K; }
 
@@ -332,6 +509,32 @@ hipError_t launch_temper(TemperArgs a, hipStream_t s) {
     }
     hipLaunchKernelGGL((mcq_temper_kernel<GW, NP>), dim3((unsigned)((a.n_ladders + lpb - 1) / lpb)), dim3(threads), bytes, s, a);
     return hipGetLastError();
+}
+
+template <int NP, int R>
+hipError_t launch_temper_counters(const TemperArgs& a, hipStream_t s) {
+    constexpr int threads = temper_threads(R, 16), lpb = threads / (R * 16);
+    const size_t bytes = (size_t)lpb * a.ladder_words * 4;
+    if (bytes > 32 * 1024) {  // (the default limit is 64 KiB; a ladder takes up to 154 816 bytes)
+        const hipError_t e = hipFuncSetAttribute((const void*)mcq_temper_counters_kernel<NP, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((mcq_temper_counters_kernel<NP, R>), dim3((unsigned)((a.n_ladders + lpb - 1) / lpb)), dim3(threads), bytes, s, a);
+    return hipGetLastError();
+}
+
+template <int NP>
+hipError_t launch_temper_counters_of(const TemperArgs& a, hipStream_t s) {
+    return a.R == 2 ? launch_temper_counters<NP, 2>(a, s) : a.R == 4 ? launch_temper_counters<NP, 4>(a, s)
+         : a.R == 8 ? launch_temper_counters<NP, 8>(a, s) : launch_temper_counters<NP, 16>(a, s);
+}
+
+// the parameter block as the kernels take it; `words` = the dwords of LDS of one ladder
+TemperArgs temper_args(const mcq_temper* q, long long words) {
+    return TemperArgs{q->seeds, q->table, q->swap_table, q->rung_in, q->rung_out, q->state_in, q->state_out, q->energy_in, q->energy_out, q->best_energy,
+                      q->best_sweep, q->best_state, q->n_changed, q->energy_hist, q->n_exchanges, q->rung_hist, q->pair_accepted, (long long)q->hist_stride,
+                      (long long)(q->n_chains / q->replicas), (long long)q->n_sweeps, (long long)q->first_sweep, (long long)q->exchange_every,
+                      (long long)(q->first_sweep / q->exchange_every), (int)q->table_len, (int)q->swap_len, (int)q->replicas, (int)words, (int)q->N};
 }
 
 // one chain's sweep on the host with the row T: mcq_heatbath_host's, E and n_changed moved
@@ -451,10 +654,7 @@ int mcq_temper_device(const mcq_temper* q, void* hip_stream) {
     if (N > 64 || bytes > MCQ_MAX_TEMPER_LDS)
         return fail(g_temper_err, MCQ_EINVAL, "N = %d with replicas = %d: a ladder takes %lld bytes of LDS, above the %d of a workgroup (mcq_temper_device runs N <= 32 with "
                     "every ladder and N <= 64 with 2 or 4 replicas; mcq_temper_host runs every N)", N, R, bytes, MCQ_MAX_TEMPER_LDS);
-    const TemperArgs a{q->seeds, q->table, q->swap_table, q->rung_in, q->rung_out, q->state_in, q->state_out, q->energy_in, q->energy_out, q->best_energy,
-                       q->best_sweep, q->best_state, q->n_changed, q->energy_hist, q->n_exchanges, q->rung_hist, q->pair_accepted, (long long)q->hist_stride,
-                       (long long)(q->n_chains / R), (long long)q->n_sweeps, (long long)q->first_sweep, (long long)q->exchange_every,
-                       (long long)(q->first_sweep / q->exchange_every), D, (int)q->swap_len, R, (int)words, N};
+    const TemperArgs a = temper_args(q, words);
     hipStream_t s = (hipStream_t)hip_stream;
     hipError_t e;
     if (N <= 8) e = launch_temper<16, 8>(a, s);
@@ -464,6 +664,20 @@ int mcq_temper_device(const mcq_temper* q, void* hip_stream) {
     else if (N <= 32) e = launch_temper<32, 32>(a, s);
     else e = launch_temper<64, 64>(a, s);
     if (e != hipSuccess) return fail(g_temper_err, MCQ_EDEVICE, "mcq_temper_device: %s", hipGetErrorString(e));
+    return MCQ_OK;
+}
+
+int mcq_temper_counters_device(const mcq_temper* q, void* hip_stream) {
+    const int rc = check_temper(q);
+    if (rc != MCQ_OK) return rc;
+    if (q->N > MCQ_MAX_N_TEMPER_COUNTERS)
+        return fail(g_temper_err, MCQ_EINVAL, "N = %d: the counter form of the tempered heat-bath sweep runs N <= %d (MCQ_MAX_N_TEMPER_COUNTERS); mcq_temper_device runs "
+                    "every N a ladder fits", (int)q->N, MCQ_MAX_N_TEMPER_COUNTERS);
+    const int N = q->N;
+    const TemperArgs a = temper_args(q, counters_ladder_words(N, (int)q->replicas, (int)q->table_len));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const hipError_t e = N <= 8 ? launch_temper_counters_of<8>(a, s) : N <= 12 ? launch_temper_counters_of<12>(a, s) : launch_temper_counters_of<16>(a, s);
+    if (e != hipSuccess) return fail(g_temper_err, MCQ_EDEVICE, "mcq_temper_counters_device: %s", hipGetErrorString(e));
     return MCQ_OK;
 }
 

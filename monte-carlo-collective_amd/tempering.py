@@ -22,11 +22,25 @@ Out of scope for both, and refused or absent rather than approximated: the drive
 import numpy as np
 
 from . import _lib, abi
-from .heatbath import _host_seeds, _upload, to_numpy  # noqa: F401  (to_numpy: the dict temper_device returned, as NumPy arrays)
+from .heatbath import FORMS, _host_seeds, _upload, to_numpy  # noqa: F401  (to_numpy: the dict temper_device returned, as NumPy arrays)
 from .quench import _device_out, _device_queens, _device_states, _host_outputs, _host_queens, _host_states, _queens_of
 
 FIELDS = ("state", "energy_in", "energy_out", "best_energy", "best_sweep", "best_state", "n_changed", "rung_out", "n_exchanges", "pair_accepted")
 FIELDS_3D = FIELDS + ("flags",)
+# FORMS is heatbath.FORMS: the two kernels of the tempered board sweep.  "lines" (mcq_temper_device, every N a ladder fits, the default)
+# tests the cells of a column's four lines; "counters" (mcq_temper_counters_device, N <= abi.MAX_N_TEMPER_COUNTERS) reads per-line queen
+# counters.  Same rule, same results.
+
+
+def _check_form(form, N, mcmc_type="board"):
+    """ValueError for an unknown form, for the counter form beyond its largest N and for the counter form of full_3d placements; nothing
+    here touches the GPU."""
+    if form not in FORMS:
+        raise ValueError(f"Unknown form {form!r}: the tempered heat-bath sweep of boards has the forms {FORMS}")
+    if form == "counters" and mcmc_type == "full_3d":
+        raise ValueError(f'the tempered heat-bath queen sweep of full_3d placements has the one form "lines", got form={form!r}')
+    if form == "counters" and int(N) > abi.MAX_N_TEMPER_COUNTERS:
+        raise ValueError(f'form="counters" runs N <= {abi.MAX_N_TEMPER_COUNTERS}, got N = {int(N)}; form="lines" runs every N a ladder fits')
 
 
 def _block(N, n, n_sweeps, first_sweep, R, K, table_len, swap_len):
@@ -168,7 +182,7 @@ def _device_call(n, block, run, dtypes, states, seeds, betas, ladder, exchange_e
 
 
 def temper_device(N, states, seeds, betas=None, ladder=None, exchange_every=1, first_sweep=0, rungs=None, tables=None, out=None, trace=False,
-                  best_state=True, stream=None):
+                  best_state=True, stream=None, form="lines"):
     """mcq_temper_device on a torch uint8 tensor [n_chains][N*N] of the current device, enqueued on `stream` (default: torch's current
     stream).  Asynchronous: nothing is copied back and nothing synchronises, so the results are valid once the stream has passed the call.
     The tables come from `betas` (one beta per sweep) and `ladder` (R multipliers), built on the host and uploaded on the stream, or from
@@ -179,10 +193,14 @@ def temper_device(N, states, seeds, betas=None, ladder=None, exchange_every=1, f
     `out` may be `states` itself (in place).
     Returns a dict of tensors: `state`, `energy_in`, `energy_out`, `best_energy` int32[n_chains], `best_sweep`, `n_changed`,
     `n_exchanges` int64[n_chains], `rung_out` uint8[n_chains], `pair_accepted` int64[n_chains / R][R - 1], `best_state` unless
-    best_state=False, and with trace=True `energy_hist` int32 and `rung_hist` uint8 [n_chains][n_sweeps + 1]."""
+    best_state=False, and with trace=True `energy_hist` int32 and `rung_hist` uint8 [n_chains][n_sweeps + 1].  `form` is one of FORMS:
+    "counters" runs mcq_temper_counters_device (N <= 16; the same results bit for bit); an unknown form, or "counters" with a larger N,
+    is a ValueError before anything else is looked at."""
+    _check_form(form, N)
     n = _device_states("temper_device", N, states)
     K = int(exchange_every)
-    return _device_call(n, lambda n_sweeps, R, D, DX: _block(N, n, n_sweeps, first_sweep, R, K, D, DX), _lib.temper_device, abi.TEMPER_DTYPES, states,
+    run = _lib.temper_counters_device if form == "counters" else _lib.temper_device
+    return _device_call(n, lambda n_sweeps, R, D, DX: _block(N, n, n_sweeps, first_sweep, R, K, D, DX), run, abi.TEMPER_DTYPES, states,
                         seeds, betas, ladder, K, first_sweep, rungs, tables, out, trace, best_state, stream)
 
 
@@ -202,7 +220,7 @@ def temper_queens_device(N, states, seeds, betas=None, ladder=None, Q=None, exch
                         states, seeds, betas, ladder, K, first_sweep, rungs, tables, out, trace, best_state, stream)
 
 
-def temper_states(N, states, seeds, betas, ladder, exchange_every=1, first_sweep=0, rungs=None, trace=False):
+def temper_states(N, states, seeds, betas, ladder, exchange_every=1, first_sweep=0, rungs=None, trace=False, form="lines"):
     """Tempered heat-bath sweeps of board placements on the GPU: `states` is uint8[n_chains][N*N], bytes >= N are clamped to N - 1;
     `seeds` one uint32 per chain; `betas` one beta >= 0 per sweep (len(betas) sweeps with the global indices first_sweep, ...); `ladder`
     R = 2, 4, 8 or 16 finite, positive, non-decreasing multipliers: chains [g R, (g + 1) R) form ladder g, and a slot on rung t runs
@@ -211,7 +229,9 @@ def temper_states(N, states, seeds, betas, ladder, exchange_every=1, first_sweep
     r % R) -- with first_sweep and the placements what a later call carries over.
     Returns a dict of NumPy arrays with the keys of FIELDS -- those of heatbath_states, `rung_out` uint8[n_chains], `n_exchanges`
     int64[n_chains], `pair_accepted` int64[n_chains / R][R - 1] -- and with trace=True `energy_hist` and `rung_hist`
-    [n_chains][len(betas) + 1].  ValueError for what the library refuses and for a ladder or a beta abi.temper_tables refuses."""
+    [n_chains][len(betas) + 1].  ValueError for what the library refuses and for a ladder or a beta abi.temper_tables refuses.
+    `form` is temper_device's: "lines" or "counters" (N <= 16), the same results."""
+    _check_form(form, N)
     import torch
 
     s = _host_states(N, states)
@@ -224,7 +244,7 @@ def temper_states(N, states, seeds, betas, ladder, exchange_every=1, first_sweep
     if s.shape[0] == 0:
         _lib.temper_host(_block(N, 0, 0, first_sweep, T.shape[1], exchange_every, 1, 1))  # raises the library's refusal
     dev = torch.device("cuda", torch.cuda.current_device())
-    res = temper_device(N, torch.from_numpy(s).to(dev), seeds, betas, ladder, exchange_every, first_sweep, rungs=rungs, trace=trace)
+    res = temper_device(N, torch.from_numpy(s).to(dev), seeds, betas, ladder, exchange_every, first_sweep, rungs=rungs, trace=trace, form=form)
     torch.cuda.current_stream(dev).synchronize()
     return to_numpy(res)
 
@@ -266,7 +286,8 @@ def ladder_statistics(res, n_events):
     return {"pair_rate": rate, "exchanges_per_slot": float(np.asarray(res["n_exchanges"]).mean())}
 
 
-def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_every=1, quench=False, trace=False, mcmc_type="board", Q=None):
+def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_every=1, quench=False, trace=False, mcmc_type="board", Q=None,
+                    form="lines"):
     """Every ladder of `seeds` for n_sweeps tempered heat-bath sweeps under one beta schedule, beta of sweep s =
     abi.beta_values(schedule_params, n_sweeps)[s] times the multiplier of the slot's rung: ONE launch.  `init` is an init mode of the
     reference ("random", "latin", "klarner": the start placements anneal_heatbath makes) or a uint8 array [n_chains][N*N].
@@ -280,7 +301,12 @@ def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_
     mcmc_type="full_3d" (default "board": everything above) runs tempered heat-bath QUEEN sweeps of Q queens in the cube (Q=None: N^2)
     through temper_queens_device: the placements are uint8[n_chains][3 Q], the start placements those of
     start_chains(..., mcmc_type="full_3d") or given ones, as anneal_heatbath makes them, the result also holds `flags`, and quench=True
-    goes through quench.quench_queens_device."""
+    goes through quench.quench_queens_device.
+
+    form (one of FORMS, default "lines") is the kernel the board launch runs through (temper_device's `form`; the results do not depend
+    on it); "counters" needs N <= 16, and full_3d placements have the one form "lines".  An unknown form or one the placements do not
+    have is a ValueError before anything else is looked at."""
+    _check_form(form, N, mcmc_type)
     import torch
 
     from . import quench as _quench
@@ -331,7 +357,7 @@ def anneal_tempered(N, n_sweeps, init, schedule_params, seeds, ladder, exchange_
         if cube:
             seg = temper_queens_device(N, state, seeds, beta, tables=tables, Q=Qn, exchange_every=K, out=state, trace=trace, stream=st)
         else:
-            seg = temper_device(N, state, seeds, beta, tables=tables, exchange_every=K, out=state, trace=trace, stream=st)
+            seg = temper_device(N, state, seeds, beta, tables=tables, exchange_every=K, out=state, trace=trace, stream=st, form=form)
         if quench:
             if cube:
                 quenched = _quench.quench_queens_device(N, seg["best_state"], Q=Qn, conflicts=False, stream=st)
