@@ -945,6 +945,82 @@ int mcq_quench_pairs_device(const mcq_quench_pairs* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
 int mcq_quench_pairs_host(const mcq_quench_pairs* q);
 
+/*
+ * Basin hopping (iterated local search) of board placements: kick a few columns of a minimum, descend again, keep the new minimum
+ * when it is no worse and go back otherwise (csrc/mcq_hop.hip) -- NOT a mode of the reference; never a default, like Philox, replica
+ * exchange, population annealing, the quenches, the heat baths and the tempered sweeps.  The thermal searches end on minima that
+ * mcq_quench and mcq_quench_pairs certify; this block goes on from a minimum.  Boards only.  The rule is integer-exact:
+ *   1. every input byte is clamped to N - 1 first; a(c, k), E, "aligned" and att are those of the mcq_quench rule, items 1 - 2, and
+ *      of the mcq_quench_pairs rule, item 1.
+ *   2. LOCAL SEARCH L, by local_search:
+ *        MCQ_HOP_SINGLE  the DESCENT of mcq_quench_pairs, item 2: passes of the mcq_quench rule until one moves nothing
+ *                        (mcq_quench with max_passes = 0);
+ *        MCQ_HOP_PAIRS   the whole mcq_quench_pairs run with max_rounds = 0: descent, scan, apply and descent again, until a scan
+ *                        finds no improving pair.
+ *      A placement that L returns is a fixed point of L: L moves nothing on it.
+ *   3. a call first applies L to the clamped input: energy_in is the recount before it, energy_start is E behind it.  Then it runs
+ *      n_hops hops; hop t = 0 .. n_hops - 1 of the call has the GLOBAL index g = first_hop + t.
+ *   4. KICK of hop g, with m = kick (1 .. MCQ_MAX_HOP_KICK): for q = 0 .. m - 1 in order, with x1 = word 2 (g m + q) and
+ *      x2 = word 2 (g m + q) + 1 of the chain's stream,  c = floor(x1 N^2 / 2^32),  k = floor(x2 N / 2^32),  and h(c) = k.  Later
+ *      kicks of the hop see earlier ones; a column may be drawn twice; k may equal h(c).  Word w (64-bit) of chain r is
+ *        philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[r], 5))[w % 4]
+ *      (key words 0 - 4 are taken by the sweep, the two heat baths and the two tempered sweeps).
+ *   5. L runs on the kicked placement and gives E'.  The hop is ACCEPTED when E' <= E + slack, E the energy BEFORE the kick: the
+ *      placement and E' stay.  Otherwise every height returns to what it was before the kick, and so does E.  n_accepted counts the
+ *      accepted hops, those that land on the placement they left too.
+ *   6. best_energy = energy_start, best_hop = 0 and best_state = the placement behind item 3 to begin with.  An accepted hop with E'
+ *      strictly below best_energy sets best_energy, best_hop = t + 1 (relative to the call) and best_state, and counts in n_improved.
+ *      energy_hist[r][0 .. n_hops] holds energy_start, then E after each hop.
+ *   7. n_moves and n_pair_moves count the single and pair moves of every L of the call: that of item 3 and those of rejected hops
+ *      too.
+ * Consequences: n_hops = 0 is L alone -- mcq_quench_pairs with max_rounds = 0 (MCQ_HOP_PAIRS) or mcq_quench with max_passes = 0
+ * (MCQ_HOP_SINGLE).  The state of a chain is its placement plus a hop index and nothing else: a run cut into calls, each fed the
+ * state_out of the one before and first_hop carried over, is the unbroken run, because item 3 moves nothing on a fixed point of L.
+ * (Of the cut run's figures n_accepted, n_moves and n_pair_moves add up, energy_out and state are the last call's, and best_* are
+ * those of the FIRST call with the smallest best_energy, its best_hop moved by the hops before that call.  n_improved does not add
+ * up when slack > 0: a call counts against its own energy_start, which may lie above an earlier call's best_energy; the whole run's
+ * count is the number of new lows of the joined energy_hist.)  Chains do not interact, so state_out may be
+ * state_in.  N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS on the device and in host code alike.
+ */
+#define MCQ_HOP_SINGLE 0
+#define MCQ_HOP_PAIRS 1
+#define MCQ_MAX_HOP_KICK 1024
+typedef struct mcq_hop {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS */
+    int32_t mode;           /* MCQ_MODE_BOARD; anything else is MCQ_EINVAL */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_hops;         /* >= 0; 0 = L alone */
+    int64_t first_hop;      /* >= 0: the global index of the call's first hop; 2 kick (first_hop + n_hops) < 2^63 */
+    int32_t kick;           /* 1 .. MCQ_MAX_HOP_KICK: the draws of one kick */
+    int32_t slack;          /* >= 0: a hop may raise E by this much */
+    int32_t local_search;   /* MCQ_HOP_SINGLE or MCQ_HOP_PAIRS */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;     /* [n_chains][N*N]; may be state_in */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_start;  /* optional [n_chains]: E behind the first L */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* best_energy;   /* optional [n_chains] */
+    int64_t* best_hop;      /* optional [n_chains]: 0 = the placement behind the first L, t + 1 = behind hop t of the call */
+    uint8_t* best_state;    /* optional [n_chains][N*N]; neither state_in nor state_out */
+    int64_t* n_accepted;    /* optional [n_chains] */
+    int64_t* n_improved;    /* optional [n_chains] */
+    int64_t* n_moves;       /* optional [n_chains]: single moves of every L */
+    int64_t* n_pair_moves;  /* optional [n_chains]: pair moves of every L (0 under MCQ_HOP_SINGLE) */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_hops */
+    int64_t hist_stride;    /* >= n_hops + 1 when energy_hist is given; not read otherwise */
+} mcq_hop;
+
+/* the message of the last error of the calling thread from the two mcq_hop_* calls below (they do not set mcq_last_error()) */
+const char* mcq_hop_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_hops is; asynchronous: nothing is
+ * copied back and nothing synchronises.  MCQ_EINVAL before any launch: mode other than board, N out of range, n_chains outside
+ * 1 .. 2^31 - 1, a negative n_hops, first_hop or slack, kick outside 1 .. MCQ_MAX_HOP_KICK, 2 kick (first_hop + n_hops) >= 2^63, a
+ * local_search that is neither value, a NULL seeds, state_in or state_out, hist_stride below n_hops + 1 when energy_hist is given. */
+int mcq_hop_device(const mcq_hop* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+int mcq_hop_host(const mcq_hop* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

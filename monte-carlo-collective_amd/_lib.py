@@ -219,6 +219,11 @@ def lib():
         L.mcq_quench_pairs_device.argtypes = [C.POINTER(abi.QuenchPairs), C.c_void_p]
         L.mcq_quench_pairs_host.restype = C.c_int
         L.mcq_quench_pairs_host.argtypes = [C.POINTER(abi.QuenchPairs)]
+        L.mcq_hop_last_error.restype = C.c_char_p
+        L.mcq_hop_device.restype = C.c_int
+        L.mcq_hop_device.argtypes = [C.POINTER(abi.Hop), C.c_void_p]
+        L.mcq_hop_host.restype = C.c_int
+        L.mcq_hop_host.argtypes = [C.POINTER(abi.Hop)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -318,6 +323,28 @@ def quench_pairs_host(q):
 def quench_pairs_device(q, stream):
     """mcq_quench_pairs_device on a filled abi.QuenchPairs block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_quench_pairs(lib().mcq_quench_pairs_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_hop(rc):
+    """_check for the mcq_hop_* calls, which keep their own message (mcq_hop_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_hop_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def hop_host(q):
+    """mcq_hop_host on a filled abi.Hop block of HOST pointers.  Pure host code, no GPU."""
+    _check_hop(lib().mcq_hop_host(C.byref(q)))
+
+
+def hop_device(q, stream):
+    """mcq_hop_device on a filled abi.Hop block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_hop(lib().mcq_hop_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def _check_quench3d(rc):

@@ -192,6 +192,45 @@ QUENCH_PAIRS_DTYPES = {"energy_in": np.int32, "energy_single": np.int32, "energy
                        "n_rounds": np.int32, "certified": np.int32, "conflicts": np.uint16}
 
 
+HOP_SINGLE, HOP_PAIRS = 0, 1   # include/mcq.h: MCQ_HOP_SINGLE, MCQ_HOP_PAIRS
+MAX_HOP_KICK = 1024            # MCQ_MAX_HOP_KICK
+HOP_LOCAL_SEARCH = {"single": HOP_SINGLE, "pairs": HOP_PAIRS}
+
+
+class Hop(C.Structure):
+    """include/mcq.h: mcq_hop -- basin hopping of board placements: kick, local search, keep the new minimum when it is no worse"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_hops", C.c_int64),
+        ("first_hop", C.c_int64),
+        ("kick", C.c_int32),
+        ("slack", C.c_int32),
+        ("local_search", C.c_int32),
+        ("seeds", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_start", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_hop", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_accepted", C.c_void_p),
+        ("n_improved", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_pair_moves", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+    ]
+
+
+# the per-chain outputs of a hop call besides the placements (state, best_state): field -> dtype ("energy_hist" has a row of n_hops + 1 per chain)
+HOP_DTYPES = {"energy_in": np.int32, "energy_start": np.int32, "energy_out": np.int32, "best_energy": np.int32, "best_hop": np.int64,
+              "n_accepted": np.int64, "n_improved": np.int64, "n_moves": np.int64, "n_pair_moves": np.int64, "energy_hist": np.int32}
+
+
 MAX_N_QUENCH3D = 32            # include/mcq.h: MCQ_MAX_N_QUENCH3D
 QUENCH3D_REPEATED = 1          # MCQ_QUENCH3D_REPEATED: bit 0 of flags
 

@@ -245,7 +245,7 @@ def write_best_heights(heights, N, path):
 
 def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.0, base_seed=42, init_mode="random",
                     out_dir="competition_results", runner=None, timestamp=None, resample_every=None, population=None, resample_seed=0, quench=False,
-                    heatbath_sweeps=None, heatbath_form="lines"):
+                    heatbath_sweeps=None, heatbath_form="lines", hops=0, hop_kick=2):
     """competition.py:143-187: board chains with linear annealing beta_start -> beta_end, seeds base_seed + r; the board
     of the run with the lowest best energy is written to {out_dir}/best_heights_{N}_{timestamp}.txt.
     Returns (best energy, heights, path).
@@ -266,30 +266,45 @@ def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.
     (heatbath.anneal_heatbath) instead of n_steps Metropolis steps, beta_start -> beta_end over the sweeps, from the same initial
     placements; resample_every (then in sweeps), population, resample_seed and quench are honoured; `n_steps` and `runner` are unused.
     heatbath_form ("lines" or "counters", N <= 16) is anneal_heatbath's `form`: the kernel of the sweeps, not their result; unused
-    without heatbath_sweeps."""
+    without heatbath_sweeps.
+
+    hops=K (not in the reference; 0 = nothing changes): the best_state of every run, from whichever search ran, goes through K hops of
+    basin hopping on the device (quench.hop_states: `hop_kick` random columns get random heights, the pair-move descent runs again, the
+    new minimum stays when it is no worse; seeds base_seed + r, a Philox key word of their own), and the board written is the hops'
+    best_state of the run with the lowest best_energy of the hops (the first such run).  The file has `_hopped` in its name, behind
+    the suffix of `quench` if there is one, and the call returns FOUR values, (energy, heights, path, info), with info = {"hopped": K,
+    "kick": hop_kick, "run": r, "energy_before": that run's best_energy, "energy_start": its energy behind the first descent,
+    "accepted", "improved", "best_hop"}; with `quench` set, info["quenched"] says which.  Boards up to N = 32."""
     from . import quench as _quench
 
     _quench.check_mode(quench, N)
+    _quench.check_hops(hops, hop_kick, N)
+
+    def _write(res, N, out_dir, timestamp, quench):
+        if not hops:
+            return _write_competition(res, N, out_dir, timestamp, quench)
+        return _write_hopped(res, N, out_dir, timestamp, quench, int(hops), int(hop_kick), ex.abi.seeds_for(base_seed, n_runs))
+
     sp = {"type": "linear_annealing", "beta_start": beta_start, "beta_end": beta_end}
     if heatbath_sweeps is not None:
         from . import heatbath as _hb
 
         res = _hb.anneal_heatbath(N, heatbath_sweeps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), resample_every=resample_every,
                                   population=population, resample_seed=resample_seed, quench=quench, form=heatbath_form)
-        return _write_competition(res[0] if resample_every is not None else res, N, out_dir, timestamp, quench)
+        return _write(res[0] if resample_every is not None else res, N, out_dir, timestamp, quench)
     if resample_every is not None:
         from . import population as _pop
 
         res, _ = _pop.anneal_population(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), resample_every, population=population,
                                         resample_seed=resample_seed, mcmc_type="board", trace=False, states=True, quench=quench)
-        return _write_competition(res, N, out_dir, timestamp, quench)
+        return _write(res, N, out_dir, timestamp, quench)
     runner = _runner_or_default(runner)
     try:
         res, _ = runner(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), mcmc_type="board", early_stop_patience=None,
                         trace=False, states=True)
     except TypeError:  # injected runners without a `states` argument return the states anyway
         res, _ = runner(N, n_steps, init_mode, sp, ex.abi.seeds_for(base_seed, n_runs), mcmc_type="board", early_stop_patience=None, trace=False)
-    return _write_competition(res, N, out_dir, timestamp, quench)
+    return _write(res, N, out_dir, timestamp, quench)
 
 
 def _write_competition(res, N, out_dir, timestamp, quench=False):
@@ -320,6 +335,25 @@ def _write_competition(res, N, out_dir, timestamp, quench=False):
     heights = np.asarray(res["best_state"][r]).reshape(N, N)
     path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}.txt"))
     return int(res["best_energy"][r]), heights, path
+
+
+def _write_hopped(res, N, out_dir, timestamp, quench, hops, hop_kick, seeds):
+    """run_competition with hops: the runs' best_state through the hops, and the best of what they reach to the file."""
+    import time
+
+    from . import quench as _quench
+
+    stamp = timestamp if timestamp is not None else time.strftime("%Y%m%d_%H%M%S")
+    h = _quench.hop_states(N, np.asarray(res["best_state"]), seeds, hops, kick=hop_kick)
+    r = int(np.argmin(h["best_energy"]))
+    heights = np.asarray(h["best_state"][r]).reshape(N, N)
+    suffix = "_quenched_pairs" if quench == "pairs" else "_quenched" if quench else ""
+    path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}{suffix}_hopped.txt"))
+    info = {"hopped": hops, "kick": hop_kick, "run": r, "energy_before": int(res["best_energy"][r]), "energy_start": int(h["energy_start"][r]),
+            "accepted": int(h["n_accepted"][r]), "improved": int(h["n_improved"][r]), "best_hop": int(h["best_hop"][r])}
+    if quench:
+        info["quenched"] = "pairs" if quench == "pairs" else True
+    return int(h["best_energy"][r]), heights, path, info
 
 
 def load_config(path="config.yaml"):

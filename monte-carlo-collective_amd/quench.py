@@ -11,6 +11,10 @@ quench_pairs, quench_pairs_device and quench_pairs_host go one neighbourhood fur
 csrc/mcq_quench_pairs.hip): the descent also takes moves of two aligned columns at once and ends on a placement that no single move
 and no pair move lowers.  Boards, N = 2 .. 32; opt-in like everything here.
 
+hop_states, hop_device and hop_host go on from a minimum (include/mcq.h: mcq_hop; csrc/mcq_hop.hip): basin hopping, that is a kick of
+a few columns, the single-move or the pair-move descent again, and the new minimum kept when it is no worse.  A whole run of hops is
+one launch.  Boards, N = 2 .. 32; opt-in like everything here.
+
 full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_quench3d; csrc/mcq_quench3d.hip), N = 2 .. 32 and
 2 <= Q <= N^3 - 1: quench_queens, quench_queens_device, quench_queens_host.  The same labels apply -- the reference ships
 conflicts_for_queen (mcmc.py:185-226) and never calls it.
@@ -220,6 +224,110 @@ def quench_pairs(N, states, max_rounds=0, conflicts=True):
     res = quench_pairs_device(N, torch.from_numpy(s).to(dev), max_rounds=max_rounds, conflicts=conflicts)
     torch.cuda.current_stream(dev).synchronize()
     return to_numpy(res)
+
+
+FIELDS_HOP = ("state", "energy_in", "energy_start", "energy_out", "best_energy", "best_hop", "best_state", "n_accepted", "n_improved", "n_moves",
+              "n_pair_moves", "energy_hist")
+
+
+def _block_hop(N, n, n_hops, kick, slack, local_search, first_hop):
+    if local_search not in abi.HOP_LOCAL_SEARCH:
+        raise ValueError(f'local_search must be "single" or "pairs", got {local_search!r}')
+    q = abi.Hop()
+    q.N, q.mode, q.n_chains, q.n_hops, q.first_hop = int(N), abi.MODE_BOARD, int(n), int(n_hops), int(first_hop)
+    q.kick, q.slack, q.local_search = int(kick), int(slack), abi.HOP_LOCAL_SEARCH[local_search]
+    return q
+
+
+def _hop_seeds(seeds, n):
+    s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+    if s.shape[0] != n:
+        raise ValueError(f"seeds must be uint32[n_chains = {n}], got {s.shape[0]}")
+    return s
+
+
+def hop_host(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, hist=False):
+    """mcq_hop_host: basin hopping in the library's plain host code, NumPy in and out, no GPU.  Same result as hop_states."""
+    s = _host_states(N, states)
+    n = s.shape[0]
+    sd = _hop_seeds(seeds, n)
+    q = _block_hop(N, n, n_hops, kick, slack, local_search, first_hop)
+    width = max(int(n_hops), 0) + 1
+    out = _host_outputs(q, s, abi.HOP_DTYPES, {"energy_hist": (n, width)}, () if hist else ("energy_hist",), like=("best_state",))
+    q.seeds, q.hist_stride = sd.ctypes.data, width
+    _lib.hop_host(q)
+    return out
+
+
+def hop_device(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, hist=False, out=None, stream=None):
+    """mcq_hop_device on a torch uint8 tensor [n_chains][N*N] of the current device (e.g. DeviceRun.t["best_state"]) and an int32 or
+    uint32 tensor `seeds` [n_chains] on the same device (the seeds' 32 bits, whatever the sign), enqueued on `stream` (default: torch's
+    current stream).  ONE kernel whatever n_hops is.  Asynchronous: nothing is copied back and nothing synchronises.  `out` (optional)
+    is the tensor the final placements go to; it may be `states` itself (in place), default a new one.  Returns a dict of tensors with
+    the fields of FIELDS_HOP: `state` and `best_state` uint8 like `states`; `energy_in`, `energy_start`, `energy_out`, `best_energy`
+    int32[n_chains]; `best_hop`, `n_accepted`, `n_improved`, `n_moves`, `n_pair_moves` int64[n_chains]; and with hist=True `energy_hist`
+    int32[n_chains][n_hops + 1]."""
+    import torch
+
+    n = _device_states("hop_device", N, states)
+    dev = states.device
+    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
+            and tuple(seeds.shape) == (n,)):
+        raise ValueError(f"hop_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = _block_hop(N, n, n_hops, kick, slack, local_search, first_hop)
+        width = max(int(n_hops), 0) + 1
+        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
+        for k, dt in abi.HOP_DTYPES.items():
+            if k != "energy_hist":
+                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+            elif hist:
+                res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
+        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
+        for k in abi.HOP_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.hop_device(q, st)
+    return res
+
+
+def hop_states(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, hist=False):
+    """Basin hopping of board placements on the GPU: `states` is uint8[n_chains][N*N] (one board of N*N heights is taken as one chain),
+    bytes >= N are clamped to N - 1; `seeds` is uint32[n_chains].  Every placement first descends to a minimum of the local search --
+    "single": single-height moves, "pairs": those and moves of two aligned columns --; then n_hops times `kick` random columns get
+    random heights, the local search runs again, and the new minimum stays when its energy is at most the old one + slack; otherwise
+    the placement goes back.  Returns a dict of NumPy arrays with the fields of FIELDS_HOP (`energy_hist` only with hist=True).
+    A run may be cut: feed `state` back in with first_hop = the hops done so far.  n_accepted, n_moves and n_pair_moves of the pieces add up; best_energy
+    / best_state / best_hop of the whole are those of the FIRST piece with the smallest best_energy, its best_hop moved by the hops
+    before that piece; n_improved of the whole is the number of new lows of the joined energy_hist (a piece counts against its own
+    start, which with slack > 0 may lie above an earlier piece's best_energy).  ValueError for what the library refuses (N outside 2 .. 32, no chain, kick outside 1 .. 1024, a negative
+    n_hops, first_hop or slack)."""
+    import torch
+
+    s = _host_states(N, states)
+    sd = _hop_seeds(seeds, s.shape[0])
+    if s.shape[0] == 0:
+        _lib.hop_host(_block_hop(N, 0, n_hops, kick, slack, local_search, first_hop))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = hop_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_hops, kick=kick, slack=slack,
+                     local_search=local_search, first_hop=first_hop, hist=hist)
+    torch.cuda.current_stream(dev).synchronize()
+    return to_numpy(res)
+
+
+def check_hops(hops, hop_kick, N, board=True):
+    """ValueError for what the competition driver's `hops` hook does not take, before anything is launched."""
+    if int(hops) < 0:
+        raise ValueError(f"hops must be >= 0, got {hops}")
+    if int(hops) == 0:
+        return
+    if not board:
+        raise ValueError('hops: basin hopping runs boards only (mcmc_type="board")')
+    if not abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH_PAIRS:
+        raise ValueError(f"hops: N out of range [{abi.MIN_N}, {abi.MAX_N_QUENCH_PAIRS}]: {N}")
+    if not 1 <= int(hop_kick) <= abi.MAX_HOP_KICK:
+        raise ValueError(f"hop_kick out of range [1, {abi.MAX_HOP_KICK}]: {hop_kick}")
 
 
 def check_mode(quench, N, board=True):
