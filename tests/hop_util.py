@@ -54,8 +54,9 @@ def _search_host(N, h, pairs):
 
 
 def hop(N, board, seed, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, search="numpy"):
-    """One board through the rule; returns a dict with the fields of mcq_hop plus `energy_hist`, `trace` and `drawn_twice` (hops whose
-    kick drew some column more than once)."""
+    """One board through the rule; returns a dict with the fields of mcq_hop plus `energy_hist`, `trace`, `drawn_twice` (hops whose
+    kick drew some column more than once) and `redrawn` (hops whose kick drew some column twice with DIFFERENT heights: only there does
+    the order of the draws show)."""
     L = {"numpy": _search_numpy, "host": _search_host}[search]
     pairs = {"single": False, "pairs": True}[local_search]
     h = qu.clamp(N, board).copy()
@@ -64,11 +65,12 @@ def hop(N, board, seed, n_hops, kick=2, slack=0, local_search="pairs", first_hop
     e_start = best = E
     best_hop, best_state = 0, h.copy()
     accepted = improved = 0
-    hist, trace, twice = [E], [], 0
+    hist, trace, twice, redrawn = [E], [], 0, 0
     for t in range(n_hops):
         before = h.copy()  # the copy a rejected hop is restored from
         draws = kick_draws(N, seed, first_hop + t, kick)
         twice += len({c for c, _ in draws}) < len(draws)
+        redrawn += len({c for c, _ in draws}) < len(set(draws))  # some column with two heights
         for c, k in draws:
             h[c] = k
         h, e_new, m, p = L(N, h, pairs)
@@ -88,7 +90,8 @@ def hop(N, board, seed, n_hops, kick=2, slack=0, local_search="pairs", first_hop
         hist.append(E)
     return {"state": h.astype(np.uint8), "energy_in": e_in, "energy_start": e_start, "energy_out": E, "best_energy": best, "best_hop": best_hop,
             "best_state": best_state.astype(np.uint8), "n_accepted": accepted, "n_improved": improved, "n_moves": moves,
-            "n_pair_moves": pair_moves, "energy_hist": np.array(hist, dtype=np.int64), "trace": trace, "drawn_twice": twice}
+            "n_pair_moves": pair_moves, "energy_hist": np.array(hist, dtype=np.int64), "trace": trace, "drawn_twice": twice,
+            "redrawn": redrawn, "kick": kick}
 
 
 def hop_many(N, states, seeds, n_hops, **kw):
@@ -96,6 +99,8 @@ def hop_many(N, states, seeds, n_hops, **kw):
     out = {k: np.stack([np.asarray(r[k]) for r in rows]) for k in FIELDS + ("energy_hist",)}
     out["trace"] = [r["trace"] for r in rows]
     out["drawn_twice"] = sum(r["drawn_twice"] for r in rows)
+    out["redrawn"] = sum(r["redrawn"] for r in rows)
+    out["kick"] = kw.get("kick", 2)
     return out
 
 
@@ -106,13 +111,16 @@ def assert_equal(got, want, what, hist=True):
 
 class Coverage:
     """The condition on the inputs: what the restatement's traces of a group of comparisons contain.  A group without rejected hops
-    never ran the restore path, one without accepted hops on a changed placement never ran the commit path."""
+    never ran the restore path, one without accepted hops on a changed placement never ran the commit path, and one whose kicks of three
+    draws or more never draw a column twice with different heights never showed in which order the draws of a kick are applied."""
 
     def __init__(self):
         self.count = {}
 
     def add(self, group, want):
-        c = self.count.setdefault(group, {"rejected": 0, "changed": 0, "improved": 0, "hops": 0})
+        c = self.count.setdefault(group, {"rejected": 0, "changed": 0, "improved": 0, "hops": 0, "redrawn": 0, "largest_kick": 0})
+        c["redrawn"] += want["redrawn"]
+        c["largest_kick"] = max(c["largest_kick"], want["kick"])
         for tr in want["trace"]:
             c["hops"] += len(tr)
             c["rejected"] += tr.count("rejected")
@@ -122,7 +130,41 @@ class Coverage:
     def check(self, group):
         c = self.count[group]
         assert c["rejected"] >= 3 and c["changed"] >= 3 and c["improved"] >= 1, (group, c)
+        assert c["largest_kick"] < 3 or c["redrawn"] >= 1, (group, c)
         return c
+
+
+MAX_KICK = 1024  # MCQ_MAX_HOP_KICK: more draws than any board has columns
+MAX_KICK_CASES = ((4, 3, 8, ("single", "pairs")), (12, 2, 5, ("single", "pairs")), (32, 1, 3, ("pairs",)))  # N, chains, hops, local searches
+
+_max_kick_cache = {}
+
+
+def max_kick_case(N, search, accept_all):
+    """(boards, seeds, hops, slack, the restated run) of the comparison with kick = MAX_KICK at N: every hop redraws nearly the whole board
+    (64 draws per column at N = 4), once without slack and once with a slack above every energy.  The local search is the restatement's
+    own at N = 4 and the library's quench host calls beyond.  Computed once per session, shared and left unchanged."""
+    key = (N, search, accept_all)
+    if key not in _max_kick_cache:
+        import mcq_amd
+
+        n, hops = next((c[1], c[2]) for c in MAX_KICK_CASES if c[0] == N)
+        s = qu.random_boards(N, n, 9 + N, over=True)
+        seeds = mcq_amd.abi.seeds_for(60 + N, n)
+        slack = 4 * N * N * N if accept_all else 0  # E <= 4 (N - 1) N^2 / 2
+        want = hop_many(N, s, seeds, hops, kick=MAX_KICK, slack=slack, local_search=search, search="numpy" if N == 4 else "host")
+        _max_kick_cache[key] = (s, seeds, hops, slack, want)
+    return _max_kick_cache[key]
+
+
+def mark_first_hop(kick, before=2):
+    """A first_hop `before` hops short of the hop whose kick holds word 2^35 of the stream: there w >> 34, the second counter word of the
+    block of word w, goes from 1 to 2 (rule item 4: the high bits of w / 4)."""
+    return (1 << 35) // (2 * kick) - before
+
+
+def crosses_the_mark(kick, first_hop, n_hops):
+    return (2 * kick * first_hop) >> 34 == 1 and (2 * kick * (first_hop + n_hops) - 1) >> 34 == 2
 
 
 def merge(parts):

@@ -1,7 +1,12 @@
 """GPU: the basin-hopping kernel (mcq_hop_device) against the library's host code (mcq_hop_host) bit for bit on every output at both ends
 of every instantiation, for both local searches; a cut run, in place, a stream of its own, and the run_competition hook against the
 composed calls.  Before a group of comparisons counts, the restatement (tests/hop_util.py) must say that it holds rejected hops,
-committed hops and an improving hop: otherwise the restore or the commit path never ran."""
+committed hops, an improving hop and a kick that draws a column twice with different heights: otherwise the restore or the commit path
+never ran, or the order of a kick's draws never showed.
+
+Beyond the host code: the stream on both sides of word 2^35 and kick = MCQ_MAX_HOP_KICK against the restated loop, whose words are
+Python integers; n_hops = 0 at any first_hop against the quench kernels; and at N = 17, 24, 25, 32 state and best_state certified as
+minima by the NumPy table and the exhaustive pair scan of tests/quench_pairs_util.py, not by kernels that share the code under test."""
 import functools
 import os
 
@@ -10,6 +15,7 @@ import pytest
 
 import mcq_amd
 from tests import hop_util as hu
+from tests import quench_pairs_util as qp
 from tests import quench_util as qu
 from tests import resume_util as ru
 
@@ -114,6 +120,16 @@ def test_kernel_equals_the_host_code(NP, search):
                 torch.cuda.current_stream(dev).synchronize()
                 np.testing.assert_array_equal(o2.cpu().numpy(), want["state"])
                 np.testing.assert_array_equal(t2.cpu().numpy(), s)  # out of place: the input is untouched
+            if n == 5 and kick == 3 and N >= DEEP_FROM:
+                # state and best_state are minima by a certificate that owes nothing to the library: the NumPy table for single moves and,
+                # under "pairs", the exhaustive scan of every aligned pair
+                for k in ("state", "best_state"):
+                    for r in (0, 4):
+                        if search == "pairs":
+                            qp.certify(N, got[k][r], f"{what}: {k} of chain {r}")
+                        else:
+                            assert qu.is_local_minimum(N, got[k][r]), f"{what}: {k} of chain {r} is no single-move minimum"
+                        assert qu.energy(N, got[k][r]) == int(got["best_energy" if k == "best_state" else "energy_out"][r])
 
 
 @pytest.mark.parametrize("search", SEARCHES)
@@ -150,6 +166,86 @@ def test_a_cut_run_is_the_unbroken_run(search):
         assert (np.diff(hist, axis=1) <= slack).all()
         np.testing.assert_array_equal(whole["best_energy"], hist.min(axis=1))
         np.testing.assert_array_equal(whole["best_hop"], hist.argmin(axis=1))
+
+
+def _near_minima(N, n):
+    """Boards whose local search is short at every N: those of _boards up to N = 16, minima with columns redrawn beyond."""
+    return _boards(N, n, 30 + N) if N < DEEP_FROM else qp.kicked_minima(N, n, 4, 12)
+
+
+@pytest.mark.parametrize("search", SEARCHES)
+@pytest.mark.parametrize("N,n", ((8, 65), (16, 5), (32, 2)))
+def test_the_stream_beyond_word_2_34(N, n, search):
+    """Hops on both sides of word 2^35 of the stream, where the second counter word of a block goes from 1 to 2 -- inside a kick, with
+    the odd kick --: the kernel against the host code, and against the restated loop (whose words are Python integers) on the first
+    chains; then a run cut 7 + 1 + rest across the mark."""
+    s = _near_minima(N, n)
+    seeds = abi.seeds_for(700 + N, n)
+    for kick, slack in ((3, 1), (N + 2, 0)):
+        first, hops = hu.mark_first_hop(kick), 6
+        assert hu.crosses_the_mark(kick, first, hops)
+        kw = dict(kick=kick, slack=slack, local_search=search, first_hop=first)
+        what = f"N={N} {search} kick={kick} first_hop={first}"
+        got = quench.hop_states(N, s, seeds, hops, hist=True, **kw)
+        hu.assert_equal(got, quench.hop_host(N, s, seeds, hops, hist=True, **kw), what)
+        m = min(n, 3)
+        traced = hu.hop_many(N, s[:m], seeds[:m], hops, search="host", **kw)
+        hu.assert_equal({k: v[:m] for k, v in got.items()}, traced, what + ": kernel vs the restated loop")
+        assert any(x in ("changed", "improved") for tr in traced["trace"] for x in tr), what
+    kick = 3
+    first = hu.mark_first_hop(kick, before=7)  # the kick of the single hop in the middle holds word 2^35
+    assert hu.crosses_the_mark(kick, first + 7, 1)
+    kw = dict(kick=kick, slack=1, local_search=search, hist=True)
+    whole = quench.hop_states(N, s, seeds, 14, first_hop=first, **kw)
+    parts, state, done = [], s, first
+    for hops in (7, 1, 6):
+        parts.append(quench.hop_states(N, state, seeds, hops, first_hop=done, **kw))
+        state, done = parts[-1]["state"], done + hops
+    hu.assert_equal(hu.merge(parts), whole, f"N={N} {search}: 7 + 1 + 6 hops across word 2^35")
+    hu.assert_equal(whole, quench.hop_host(N, s, seeds, 14, first_hop=first, **kw), f"N={N} {search}: 14 hops across word 2^35")
+
+
+@pytest.mark.parametrize("N,n,hops,searches", hu.MAX_KICK_CASES)
+def test_the_largest_kick(N, n, hops, searches):
+    """kick = MCQ_MAX_HOP_KICK: the kernel against the restated loop and the host code, without slack (rejections: the whole board is
+    restored) and with a slack above every energy (none)."""
+    rejected = 0
+    for search in searches:
+        for accept_all in (False, True):
+            s, seeds, _, slack, want = hu.max_kick_case(N, search, accept_all)
+            n_rej = sum(tr.count("rejected") for tr in want["trace"])
+            assert n_rej == 0 or not accept_all
+            rejected += n_rej
+            kw = dict(kick=hu.MAX_KICK, slack=slack, local_search=search, hist=True)
+            got = quench.hop_states(N, s, seeds, hops, **kw)
+            hu.assert_equal(got, want, f"N={N} {search} kick={hu.MAX_KICK} slack={slack}: kernel vs the restated loop")
+            if N < 32:  # (at N = 32 tests/test_hop_host.py holds host code = restated loop on these very inputs)
+                hu.assert_equal(got, quench.hop_host(N, s, seeds, hops, **kw), f"N={N} {search} kick={hu.MAX_KICK} slack={slack}")
+    assert rejected >= 2
+
+
+@pytest.mark.parametrize("search", SEARCHES)
+def test_no_hops_is_the_quench_at_any_first_hop(search):
+    """n_hops = 0 is the local search alone, whatever first_hop and kick say: the quench kernels' and the host code's figures."""
+    for N, n in ((6, 65), (12, 5), (17, 3), (32, 2)):
+        s = _near_minima(N, n)
+        seeds = abi.seeds_for(1, n)
+        if search == "pairs":
+            q, qh = quench.quench_pairs(N, s), quench.quench_pairs_host(N, s)
+        else:
+            q, qh = quench.quench_states(N, s), quench.quench_states_host(N, s)
+        for first_hop, kick in ((0, 2), (hu.mark_first_hop(5), 5), ((1 << 52) - 1, 1024)):
+            got = quench.hop_states(N, s, seeds, 0, kick=kick, first_hop=first_hop, local_search=search, hist=True)
+            hu.assert_equal(got, quench.hop_host(N, s, seeds, 0, kick=kick, first_hop=first_hop, local_search=search, hist=True), f"N={N} {search}")
+            for ref in (q, qh):
+                for k in ("state", "energy_in", "energy_out", "n_moves") + (("n_pair_moves",) if search == "pairs" else ()):
+                    np.testing.assert_array_equal(got[k], ref[k], err_msg=f"N={N} {search} first_hop={first_hop}: {k}")
+                np.testing.assert_array_equal(got["best_state"], ref["state"])
+                for k in ("energy_start", "best_energy"):
+                    np.testing.assert_array_equal(got[k], ref["energy_out"], err_msg=k)
+            np.testing.assert_array_equal(got["energy_hist"], q["energy_out"][:, None])
+            assert not got["best_hop"].any() and not got["n_accepted"].any() and not got["n_improved"].any()
+            assert search == "pairs" or not got["n_pair_moves"].any()
 
 
 def test_torch_tensors_on_a_side_stream(monkeypatch):

@@ -1,6 +1,8 @@
 """CPU-only: basin hopping in host code (mcq_hop_host) against its NumPy restatement (tests/hop_util.py) on every output; n_hops = 0
-against the two quenches; a cut run against the unbroken one; the properties of the outputs; kicks that draw a column twice; every
-refusal; the layout of the mcq_hop block; and that the compared runs contain rejected, committed and improving hops."""
+against the two quenches, at any first_hop; a cut run against the unbroken one; the stream on both sides of word 2^35, where the
+second counter word of a block changes, whole and cut; kick = MCQ_MAX_HOP_KICK compared with and without rejections; the properties of
+the outputs; kicks that draw a column twice; every refusal; the layout of the mcq_hop block; and that the compared runs contain rejected,
+committed and improving hops and, where a kick has three draws or more, a column drawn twice with different heights."""
 import ctypes
 import functools
 import os
@@ -89,6 +91,9 @@ def test_no_hops_is_the_quench(search):
     for N, n in ((3, 6), (6, 5), (12, 3), (17, 2)):
         s = qu.random_boards(N, n, 5 + N, over=True)
         got = quench.hop_host(N, s, abi.seeds_for(1, n), 0, local_search=search, hist=True)
+        for first_hop, kick in ((3, 2), (hu.mark_first_hop(5), 5), ((1 << 52) - 1, 1024)):  # no hop, no word: first_hop and kick change nothing
+            other = quench.hop_host(N, s, abi.seeds_for(2, n), 0, kick=kick, first_hop=first_hop, local_search=search, hist=True)
+            hu.assert_equal(other, got, f"N={N} {search}: n_hops=0 at first_hop={first_hop}")
         if search == "pairs":
             q = quench.quench_pairs_host(N, s, max_rounds=0)
             np.testing.assert_array_equal(got["n_pair_moves"], q["n_pair_moves"])
@@ -122,6 +127,58 @@ def test_a_cut_run_is_the_unbroken_run(search):
         assert (whole["n_improved"] > 0).any() and (whole["best_hop"] > 8).any(), "no chain improved in the later calls"
         # another first_hop is another run
         assert not np.array_equal(quench.hop_host(N, s, seeds, 30, first_hop=5, **kw)["energy_hist"], whole["energy_hist"])
+
+
+@pytest.mark.parametrize("search", SEARCHES)
+def test_the_stream_beyond_word_2_34(search):
+    """Hops whose words lie on both sides of word 2^35, where the second counter word of the block (w >> 34) goes from 1 to 2 inside the
+    run -- inside a kick, with the odd kick --, against the restatement, whose words are Python integers; then a run cut 7 + 1 + rest
+    across the same mark."""
+    for N, n, kick, slack, how in ((4, 3, 3, 1, "numpy"), (5, 2, 4, 0, "numpy"), (13, 2, 15, 2, "host"), (13, 2, 4, 0, "host")):
+        first, hops = hu.mark_first_hop(kick), 6
+        assert hu.crosses_the_mark(kick, first, hops)
+        assert kick % 2 == 0 or (1 << 35) % (2 * kick) != 0  # the odd kicks: word 2^35 is no first word of a kick
+        s = qu.random_boards(N, n, 70 + N + kick, over=True)
+        seeds = abi.seeds_for(11 + kick, n)
+        kw = dict(kick=kick, slack=slack, local_search=search, first_hop=first)
+        want = hu.hop_many(N, s, seeds, hops, search=how, **kw)
+        hu.assert_equal(quench.hop_host(N, s, seeds, hops, hist=True, **kw), want, f"N={N} {search} kick={kick} first_hop={first}")
+        assert any(x != "rejected" and x != "same" for tr in want["trace"] for x in tr), "no hop past the mark changed a placement"
+    # the restated word past the mark takes the high counter word: it is not the word of a stream that dropped it
+    w = (1 << 35) + 6
+    assert hu.word(11, w) == hb.philox(((w >> 2) & hb.MASK, 2, 0, 0), (11, 5))[2] != hb.philox(((w >> 2) & hb.MASK, 0, 0, 0), (11, 5))[2]
+    for N, n, kick, slack in ((5, 4, 3, 1), (9, 3, 11, 0)):
+        first = hu.mark_first_hop(kick, before=7)  # the kick of the single hop in the middle holds word 2^35
+        s = qu.random_boards(N, n, 40 + N, over=True)
+        seeds = abi.seeds_for(9, n)
+        kw = dict(kick=kick, slack=slack, local_search=search, hist=True)
+        assert hu.crosses_the_mark(kick, first + 7, 1)
+        whole = quench.hop_host(N, s, seeds, 20, first_hop=first, **kw)
+        parts, state, done = [], s, first
+        for hops in (7, 1, 12):
+            parts.append(quench.hop_host(N, state, seeds, hops, first_hop=done, **kw))
+            state, done = parts[-1]["state"], done + hops
+        hu.assert_equal(hu.merge(parts), whole, f"N={N} {search}: 7 + 1 + 12 hops across word 2^35")
+
+
+@pytest.mark.parametrize("N,n,hops,searches", hu.MAX_KICK_CASES)
+def test_the_largest_kick(N, n, hops, searches):
+    """kick = MCQ_MAX_HOP_KICK, more draws than columns at every N: compared, not only accepted.  Without slack some hops are rejected
+    (the whole board is restored), with a slack above every energy none is -- by the restatement's traces."""
+    assert hu.MAX_KICK == abi.MAX_HOP_KICK > N * N - 1
+    rejected = 0
+    for search in searches:
+        for accept_all in (False, True):
+            s, seeds, hops_, slack, want = hu.max_kick_case(N, search, accept_all)
+            assert hops_ == hops and want["redrawn"] == n * hops
+            n_rej = sum(tr.count("rejected") for tr in want["trace"])
+            assert not accept_all or n_rej == 0
+            rejected += n_rej
+            got = quench.hop_host(N, s, seeds, hops, kick=hu.MAX_KICK, slack=slack, local_search=search, hist=True)
+            hu.assert_equal(got, want, f"N={N} {search} kick={hu.MAX_KICK} slack={slack}")
+            if accept_all:
+                assert (got["n_accepted"] == hops).all()
+    assert rejected >= 2, "no hop was rejected without slack"
 
 
 @pytest.mark.parametrize("search", SEARCHES)
@@ -167,6 +224,7 @@ def test_a_kick_may_draw_a_column_twice():
         for search in SEARCHES:
             want = hu.hop_many(N, s, seeds, 12, kick=kick, slack=1, local_search=search)
             assert want["drawn_twice"] == 12 * n  # more draws than columns
+            assert 0 < want["redrawn"] <= want["drawn_twice"]
             hu.assert_equal(quench.hop_host(N, s, seeds, 12, kick=kick, slack=1, local_search=search, hist=True), want, f"N={N} kick={kick} {search}")
     # the later draw of a column wins: the draws of one hop by hand
     draws = hu.kick_draws(3, 11, 0, 18)

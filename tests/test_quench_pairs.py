@@ -1,6 +1,11 @@
 """GPU: the pair-move quench kernel (mcq_quench_pairs_device) against the library's host code (mcq_quench_pairs_host) bit for bit on every
 output at both ends of every instantiation, in place and on a stream of its own; through invariants alone on the best placements of a
-heat-bath run; and behind the annealing hooks (quench="pairs") against the composed calls."""
+heat-bath run; and behind the annealing hooks (quench="pairs") against the composed calls.
+
+Held independently of the library: at N = 17, 24, 25, 32 the kernel runs to certified = 1 and equals the NumPy restatement with the
+exhaustive scan (tests/quench_pairs_util.py) on inputs whose coverage is asserted first, and its outputs pass the restatement's own
+certificate; up to N = 6 it equals the restatement with the scan over all pairs.  At N = 7 .. 16 the kernel meets the restatement only
+through the host code, which tests/test_quench_pairs_host.py compares with it at N = 8, 9, 12, 13, 16."""
 import os
 
 import numpy as np
@@ -63,6 +68,32 @@ def test_kernel_equals_the_host_code(N):
     if N <= 6:  # against the restatement too, where it is quick
         s = _boards(N, 3, 7 * N)
         qp.assert_equal(quench.quench_pairs(N, s), qp.quench_pairs_many(N, s), f"N={N} vs the restatement")
+
+
+@pytest.mark.parametrize("N", (17, 24, 25, 32))
+def test_kernel_converges_beyond_16_certified_without_the_library(N):
+    """mcq_quench_pairs_kernel<24> and <32> to certified = 1 (max_rounds = 0) on minima with a few columns redrawn: against the host code
+    and against the restatement with the exhaustive scan, on 1, 3 and 67 chains; the outputs certified by that scan and the single-move
+    table, which owe nothing to the library.  Before any of it counts, the restatement's traces of the group must hold every class of
+    pair move, every line of the board, the last dword of a table row, neighbouring columns and the second trip of the lane loop."""
+    NP = qp.padded(N)
+    cov = qp.Coverage()
+    for M in qp.GROUPS[NP]:
+        cov.add(M, qp.restated_case(M)[1])
+    print(NP, cov.check(NP, qp.GROUPS[NP][1]))
+    s, want = qp.restated_case(N)
+    host = quench.quench_pairs_host(N, s)
+    qp.assert_equal(host, want, f"N={N}: host code vs the restatement")
+    assert int(host["n_rounds"].max()) >= 3
+    for n in (1, 3, 67):
+        rows = np.arange(n) % s.shape[0]
+        got = quench.quench_pairs(N, s[rows])
+        qp.assert_equal(got, {k: host[k][rows] for k in qp.FIELDS}, f"N={N}, {n} chains, to convergence")
+        qp.assert_equal(got, {k: want[k][rows] for k in qp.FIELDS}, f"N={N}, {n} chains, vs the restatement")
+        assert (got["certified"] == 1).all() and (got["n_rounds"] == got["n_pair_moves"] + 1).all()
+    for r in (0, 1, 2, 66):  # chain 66 repeats board 0 behind the first 64 workgroups
+        qp.certify(N, got["state"][r], f"N={N} chain {r}: a certified output of the kernel")
+        assert qu.energy(N, got["state"][r]) == int(got["energy_out"][r])
 
 
 def test_pair_moves_fire_on_the_device():

@@ -1,6 +1,13 @@
 """CPU-only: the pair-move quench in host code (mcq_quench_pairs_host) against its NumPy restatement (tests/quench_pairs_util.py) on every
 output, the restatement's scan variants against each other, the properties of the output, max_rounds, in place, every refusal, the
-layout of the mcq_quench_pairs block, and that the test sets exercise pair moves at all."""
+layout of the mcq_quench_pairs block, and that the test sets exercise pair moves at all.
+
+Held independently of the library: host code = restatement to convergence at N = 2, 4, 5, 8, 9, 12, 13, 16 (random boards) and at
+N = 17, 24, 25, 32 (minima with columns redrawn; random boards for two rounds), the restatement scanning every aligned pair and every
+(k1, k2) without pruning, on inputs whose traces hold every class of pair move (D, delta1, delta2), every line of the board and the
+edges of the kernel's table rows and lane loops; and "certified = 1 means no single move and no pair move lowers E" on every output of
+test_properties_of_the_output up to N = 32.  Not held: runs to convergence from RANDOM boards beyond N = 16 (a minute each in NumPy);
+recounted energies in the scan beyond N = 5 (the formula is pinned to the recount entry for entry up to N = 6)."""
 import ctypes
 import os
 import subprocess
@@ -44,6 +51,69 @@ def test_host_code_equals_the_restatement(N, n):
         assert len(want["deltas"][r]) == int(got["n_pair_moves"][r]) and all(D in (-1, -2) for D in want["deltas"][r])
         assert int(got["energy_out"][r]) <= int(got["energy_single"][r]) + sum(want["deltas"][r])  # the descents in between lower it further
         assert qu.energy(N, got["state"][r]) == int(got["energy_out"][r])
+
+
+def _covered(NP):
+    """The coverage of group NP from the restatement's traces alone, asserted; every class is required of every group (12 random boards
+    at N = 4 do hold a (-1, 0, 0), so no group excepts one)."""
+    cov = qp.Coverage()
+    for N in qp.GROUPS[NP]:
+        cov.add(N, qp.restated_case(N)[1])
+    return cov.check(NP, qp.GROUPS[NP][1])
+
+
+@pytest.mark.parametrize("NP", sorted(qp.GROUPS))
+def test_host_code_equals_the_restatement_at_every_instantiation(NP):
+    """Both ends of every padded edge of the kernel, to convergence, against the restatement with the exhaustive vectorised scan: random
+    boards up to N = 16, minima with a few columns redrawn beyond (and random boards for two rounds there).  The inputs must hold every
+    class of pair move, every line of the board, the last heights of a table row, neighbouring columns, runs of several rounds and,
+    beyond N = 16, a second column past the 64th slot -- by the restatement's traces, before the comparison counts."""
+    print(NP, _covered(NP))
+    for N in qp.GROUPS[NP]:
+        s, want = qp.restated_case(N)
+        assert int(s.max()) >= N
+        got = quench.quench_pairs_host(N, s)
+        qp.assert_equal(got, want, f"N={N} ({s.shape[0]} boards)")
+        assert (got["certified"] == 1).all()
+        for r in range(s.shape[0] if N <= 16 else 1):
+            qp.certify(N, got["state"][r], f"N={N} board {r}")
+            assert qu.energy(N, got["state"][r]) == int(got["energy_out"][r])
+        if N > 16:  # from random boards, where the first descent is long and the first scans see many candidates
+            s = qu.random_boards(N, 1, 300 + N, over=True)
+            want = qp.quench_pairs_many(N, s, 2, pairs="fast")
+            assert int(want["certified"][0]) == 0 and len(want["trace"][0]) == 2
+            qp.assert_equal(quench.quench_pairs_host(N, s, max_rounds=2), want, f"N={N}, a random board, max_rounds=2")
+
+
+def test_fast_scan_equals_the_slow_scans():
+    """The vectorised scan against the scan over ALL pairs with recounted energies on single-move minima at N = 2 .. 5, and against the
+    scan over all pairs by the formula at N = 6 .. 8, on the minimum and on what the first pair moves lead to."""
+    checked = improving = 0
+    for N, n, slow in ((2, 6, "recount"), (3, 10, "recount"), (4, 10, "recount"), (5, 6, "recount"), (6, 4, "formula"), (7, 3, "formula"), (8, 2, "formula")):
+        for s in qu.random_boards(N, n, 140 + N):
+            h = qu.quench(N, s)["state"].astype(np.int64)
+            for _ in range(3):
+                assert qu.is_local_minimum(N, h)
+                every = qp.scan(N, h, "all", slow)
+                assert qp.fast_scan(N, h) == every, (N, h)
+                checked += 1
+                if every[0] >= 0:
+                    break
+                improving += 1
+                h[every[1]], h[every[2]] = every[3], every[4]
+                h = qu.quench(N, h)["state"].astype(np.int64)
+    assert checked >= 60 and improving >= 20
+    # off a single-move minimum the scans differ only by pairs that are not aligned: over the aligned pairs they agree on any board
+    for N in (3, 5):
+        h = qu.clamp(N, qu.random_boards(N, 1, 90 + N)[0])
+        assert qp.fast_scan(N, h) == qp.scan(N, h, "aligned", "formula")
+    # the restated runs themselves, slow scan against fast
+    for N, n in ((4, 6), (6, 3)):
+        s = qu.random_boards(N, n, 77 + N, over=True)
+        slow, fast = qp.quench_pairs_many(N, s), qp.quench_pairs_many(N, s, pairs="fast")
+        qp.assert_equal(fast, slow, f"N={N}: restated runs")
+        assert fast["deltas"] == slow["deltas"] == [[m["D"] for m in tr] for tr in fast["trace"]]
+    assert qp.lane_slot(17, 0, 16 * 17 + 16) == 2 * 17 + 16 and qp.family(17, 16, 16 * 17) == "antidiagonal" and qp.lane_slot(5, 7, 17) == 5 + 3
 
 
 def test_klarner_board_comes_back_untouched_and_certified():
@@ -112,6 +182,7 @@ def test_properties_of_the_output():
             what = f"N={N} board {r}"
             assert qu.is_local_minimum(N, got["state"][r]), f"{what}: a certified output is no single-move minimum"
             assert qu.energy(N, got["state"][r]) == int(got["energy_out"][r]), what
+            qp.certify(N, got["state"][r], what)  # at every N: no candidate of the rule lowers a certified output
             if N <= 4:
                 assert not qp.has_improving_pair_by_recount(N, got["state"][r]), f"{what}: a pair move lowers a certified output"
         again = quench.quench_pairs_host(N, got["state"])
