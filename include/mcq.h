@@ -1021,6 +1021,84 @@ int mcq_hop_device(const mcq_hop* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
 int mcq_hop_host(const mcq_hop* q);
 
+/*
+ * Basin hopping (iterated local search) of full_3d placements: kick a few queens of a minimum to free cells, descend again, keep the
+ * new minimum when it is no worse and go back otherwise (csrc/mcq_hop3d.hip) -- NOT a mode of the reference; never a default, like
+ * everything above that is labelled so.  mcq_hop above keeps refusing full_3d: a queen here has N^3 targets, and this block has its own
+ * entry points.  The rule is integer-exact:
+ *   1. the placement (Q triples of bytes, 3 Q bytes per chain), the clamping to N - 1, REPEATED, a(q, t) and E are those of the
+ *      mcq_quench3d rule, items 1 - 2.  N = 2 .. MCQ_MAX_N_QUENCH3D and 2 <= Q <= N^3 - 1 (n_queens = 0 means N^2).
+ *   2. LOCAL SEARCH L: the mcq_quench3d run with max_passes = 0, passes of its items 3 - 4 until one moves nothing.  A placement that L
+ *      returns is a fixed point of L: L moves nothing on it.
+ *   3. a call first applies L to the clamped input: energy_in is the recount before it, energy_start is E behind it.  Then it runs
+ *      n_hops hops; hop t = 0 .. n_hops - 1 of the call has the GLOBAL index g = first_hop + t.
+ *   4. KICK of hop g, with m = kick (1 .. MCQ_MAX_HOP_KICK): for d = 0 .. m - 1 in order, with x1 = word 2 (g m + d) and
+ *      x2 = word 2 (g m + d) + 1 of the chain's stream,  n = floor(x1 Q / 2^32)  and  t = floor(x2 N^3 / 2^32), t a cell index
+ *      i N^2 + j N + k.  If cell t holds a queen at that moment the draw moves nothing -- queen n's own cell and the cells taken by
+ *      earlier draws of this hop included.  Otherwise queen n moves to cell t.  Later draws see earlier ones; a queen may be drawn
+ *      twice.  Word w (64-bit) of chain r is
+ *        philox4x32-10(counter = (low 32 bits of w / 4, high bits of w / 4, 0, 0), key = (seeds[r], 6))[w % 4]
+ *      (key words 0 - 5 are taken by the sweep, the two heat baths, the two tempered sweeps and mcq_hop).
+ *   5. L runs on the kicked placement and gives E'.  The hop is ACCEPTED iff E' <= E + slack, E the energy BEFORE the kick: the
+ *      placement and E' stay.  Otherwise every queen returns to the cell it held before the kick, and so does E.
+ *   6. best_energy, best_hop, best_state, n_accepted, n_improved and energy_hist are those of the mcq_hop rule, items 6 - 7.  n_moves
+ *      counts the single-queen moves and n_passes the passes (the last, moveless one of each L too) of every L of the call: that of
+ *      item 3 and those of rejected hops too.  n_kicked counts the draws that moved a queen.  All three are int64.
+ *   7. a REPEATED input (two queens in one cell after clamping) sets bit 0 of flags (MCQ_HOP3D_REPEATED) and is handed back unmoved:
+ *      state_out and best_state are the clamped input, energy_in = energy_start = energy_out = best_energy = the recount (a shared
+ *      cell counts as an attacking pair), every counter and best_hop are 0, and energy_hist[0 .. n_hops] all hold the recount.  No
+ *      output of the rule is such a placement.
+ * Consequences: n_hops = 0 is mcq_quench3d with max_passes = 0.  The state of a chain is its placement plus a hop index and nothing
+ * else: a run cut into calls, each fed the state_out of the one before and first_hop carried over, is the unbroken run, because item 3
+ * moves nothing on a fixed point of L (the figures of the pieces combine as under mcq_hop; n_passes of a later piece counts the one
+ * moveless pass of its item 3 on top).  Chains do not interact, so state_out may be state_in.
+ *
+ * mcq_hop3d_device keeps a chain in the LDS of one workgroup: 32 dwords, the field (one byte per cell to N = 19, 16 bits beyond), the
+ * occupancy bitmap, the queens and the queens from before the kick (16 bits each, each array rounded up to a dword):
+ *   bytes = 4 (32 + ceil(N^3 / (4 or 2)) + ceil(N^3 / 32) + 2 ceil(Q / 2)) <= MCQ_MAX_HOP3D_LDS.
+ * Every Q = N^2 fits; at N = 32 the largest Q is 23 520.
+ */
+#define MCQ_MAX_HOP3D_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_hop3d_device may take */
+#define MCQ_HOP3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) input hold the same cell; nothing was moved */
+typedef struct mcq_hop3d {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t n_queens;       /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_hops;         /* >= 0; 0 = L alone */
+    int64_t first_hop;      /* >= 0: the global index of the call's first hop; 2 kick (first_hop + n_hops) < 2^63 */
+    int32_t kick;           /* 1 .. MCQ_MAX_HOP_KICK: the draws of one kick */
+    int32_t slack;          /* >= 0: a hop may raise E by this much */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;     /* [n_chains][Q][3]; may be state_in */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_start;  /* optional [n_chains]: E behind the first L */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* best_energy;   /* optional [n_chains] */
+    int64_t* best_hop;      /* optional [n_chains]: 0 = the placement behind the first L, t + 1 = behind hop t of the call */
+    uint8_t* best_state;    /* optional [n_chains][Q][3]; neither state_in nor state_out */
+    int64_t* n_accepted;    /* optional [n_chains] */
+    int64_t* n_improved;    /* optional [n_chains] */
+    int64_t* n_moves;       /* optional [n_chains]: single-queen moves of every L */
+    int64_t* n_passes;      /* optional [n_chains]: passes of every L */
+    int64_t* n_kicked;      /* optional [n_chains]: draws that moved a queen */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_hops */
+    int64_t hist_stride;    /* >= n_hops + 1 when energy_hist is given; not read otherwise */
+    int32_t* flags;         /* optional [n_chains]: MCQ_HOP3D_* */
+} mcq_hop3d;
+
+/* the message of the last error of the calling thread from the two mcq_hop3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_hop3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_hops is; asynchronous: nothing is
+ * copied back and nothing synchronises.  MCQ_EINVAL before any launch: a NULL block, N outside 2 .. 32 (33 .. 64 named as this
+ * build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, a negative n_hops, first_hop or slack, kick
+ * outside 1 .. MCQ_MAX_HOP_KICK, 2 kick (first_hop + n_hops) >= 2^63, a NULL seeds, state_in or state_out, hist_stride below
+ * n_hops + 1 when energy_hist is given, and any (N, Q) whose chain exceeds MCQ_MAX_HOP3D_LDS (the message names N, Q and the bytes). */
+int mcq_hop3d_device(const mcq_hop3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, for every shape (no LDS here), otherwise the same refusals; needs no GPU.  Equal
+ * to the kernel bit for bit on every output. */
+int mcq_hop3d_host(const mcq_hop3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -224,6 +224,11 @@ def lib():
         L.mcq_hop_device.argtypes = [C.POINTER(abi.Hop), C.c_void_p]
         L.mcq_hop_host.restype = C.c_int
         L.mcq_hop_host.argtypes = [C.POINTER(abi.Hop)]
+        L.mcq_hop3d_last_error.restype = C.c_char_p
+        L.mcq_hop3d_device.restype = C.c_int
+        L.mcq_hop3d_device.argtypes = [C.POINTER(abi.Hop3d), C.c_void_p]
+        L.mcq_hop3d_host.restype = C.c_int
+        L.mcq_hop3d_host.argtypes = [C.POINTER(abi.Hop3d)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -345,6 +350,28 @@ def hop_host(q):
 def hop_device(q, stream):
     """mcq_hop_device on a filled abi.Hop block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_hop(lib().mcq_hop_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_hop3d(rc):
+    """_check for the mcq_hop3d_* calls, which keep their own message (mcq_hop3d_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_hop3d_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def hop3d_host(q):
+    """mcq_hop3d_host on a filled abi.Hop3d block of HOST pointers.  Pure host code, no GPU."""
+    _check_hop3d(lib().mcq_hop3d_host(C.byref(q)))
+
+
+def hop3d_device(q, stream):
+    """mcq_hop3d_device on a filled abi.Hop3d block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_hop3d(lib().mcq_hop3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def _check_quench3d(rc):

@@ -258,6 +258,54 @@ QUENCH3D_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "n_moves": np.
                    "flags": np.int32}
 
 
+MAX_HOP3D_LDS = 160 * 1024     # include/mcq.h: MCQ_MAX_HOP3D_LDS
+HOP3D_REPEATED = 1             # MCQ_HOP3D_REPEATED: bit 0 of flags
+
+
+class Hop3d(C.Structure):
+    """include/mcq.h: mcq_hop3d -- basin hopping of full_3d placements: kick queens to free cells, descend, keep the new minimum when it is no worse"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_hops", C.c_int64),
+        ("first_hop", C.c_int64),
+        ("kick", C.c_int32),
+        ("slack", C.c_int32),
+        ("seeds", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_start", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_hop", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_accepted", C.c_void_p),
+        ("n_improved", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_passes", C.c_void_p),
+        ("n_kicked", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d hop call besides the placements (state, best_state): field -> dtype ("energy_hist" has a row of n_hops + 1 per chain)
+HOP3D_DTYPES = {"energy_in": np.int32, "energy_start": np.int32, "energy_out": np.int32, "best_energy": np.int32, "best_hop": np.int64,
+                "n_accepted": np.int64, "n_improved": np.int64, "n_moves": np.int64, "n_passes": np.int64, "n_kicked": np.int64,
+                "energy_hist": np.int32, "flags": np.int32}
+
+
+def hop3d_lds_bytes(N, Q=None):
+    """The bytes of LDS a chain of mcq_hop3d_device takes (include/mcq.h, below the rule): it runs what stays within MAX_HOP3D_LDS."""
+    N = int(N)
+    Q = N * N if Q is None or int(Q) == 0 else int(Q)
+    cells, cpd = N ** 3, 4 if N <= 19 else 2
+    return 4 * (32 + -(-cells // cpd) + -(-cells // 32) + 2 * ((Q + 1) // 2))
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

@@ -255,7 +255,7 @@ def check(n_chains, n_sweeps, resample_every, population=None):
 
 
 def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=None, population=None, resample_seed=0, quench=False, trace=False,
-                    mcmc_type="board", Q=None, form="lines"):
+                    mcmc_type="board", Q=None, form="lines", hops=0, hop_kick=2):
     """Every chain of `seeds` for n_sweeps heat-bath sweeps under one beta schedule, beta of sweep s = abi.beta_values(schedule_params,
     n_sweeps)[s] (the reference's schedules, evaluated per sweep instead of per step).
 
@@ -278,6 +278,11 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     or given ones, the segments, boundaries and fold are the same, `res` also holds `flags` (of the last segment), and quench=True goes
     through quench.quench_queens_device.
 
+    hops = K > 0 (full_3d only; default 0: nothing changes) sends best_state -- the quenched one with quench=True -- through K hops of
+    quench.hop_queens_device with kick = hop_kick and slack 0 on the same stream, seeded with the seeds of the run: `res` gains
+    `hopped_state`, `hopped_energy` (the best of the hops: best_state and best_energy of that call), `hop_accepted`, `hop_improved` and
+    `hop_best_hop`.  Boards refuse it: their hops are drivers.run_competition(hops=...).
+
     form (one of FORMS, default "lines") is the kernel every board segment runs through (heatbath_device's `form`; the results do not
     depend on it); "counters" needs N <= 16, and full_3d placements have the one form "lines".
 
@@ -295,6 +300,13 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     from . import quench as _quench
 
     _quench.check_mode(quench, N, board=mcmc_type != "full_3d")
+    hops = int(hops)
+    if hops < 0:
+        raise ValueError(f"hops must be >= 0, got {hops}")
+    if hops and mcmc_type != "full_3d":
+        raise ValueError('hops: anneal_heatbath hops full_3d placements only (mcmc_type="full_3d"); boards hop through run_competition(hops=...)')
+    if hops and not 1 <= int(hop_kick) <= abi.MAX_HOP_KICK:
+        raise ValueError(f"hop_kick out of range [1, {abi.MAX_HOP_KICK}]: {hop_kick}")
 
     n_sweeps = int(n_sweeps)
     if n_sweeps < 0:
@@ -354,7 +366,7 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         dseeds = torch.from_numpy(seeds.view(np.int32).copy()).to(dev)
         dtab = device_table(beta, dev)  # the whole run's rows, uploaded once; a segment reads its slice
         hist = i32(n, n_sweeps + 1) if trace else None
-        quenched = None
+        quenched = hopped = None
         if b is None:
             seg = sweep(N, state, dseeds, dtab if n_sweeps else [], first_sweep=0, out=state, trace=trace, stream=st)  # one call, in place
             hist = seg.get("energy_hist")
@@ -403,6 +415,9 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
                 quenched = _quench.quench_queens_device(N, acc["best_state"], Q=Qn, conflicts=False, stream=st)
             else:
                 quenched = _quench.hook_device(N, acc["best_state"], quench, st)
+        if hops:  # behind the quench when there is one, whose placements it takes; same stream, nothing waited for
+            hopped = _quench.hop_queens_device(N, quenched["state"] if quenched is not None else acc["best_state"], dseeds, hops, Q=Qn,
+                                               kick=int(hop_kick), stream=st)
         st.synchronize()
 
     res = {"initial_energy": e0.cpu().numpy(), "final_energy": e1.cpu().numpy(), "final_state": state.cpu().numpy(),
@@ -414,6 +429,10 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         res["energy_hist"] = hist.cpu().numpy()
     if quenched is not None:
         _quench.hook_results(res, quenched)
+    if hopped is not None:
+        res["hopped_state"], res["hopped_energy"] = hopped["best_state"].cpu().numpy(), hopped["best_energy"].cpu().numpy()
+        res["hop_accepted"], res["hop_improved"] = hopped["n_accepted"].cpu().numpy(), hopped["n_improved"].cpu().numpy()
+        res["hop_best_hop"] = hopped["best_hop"].cpu().numpy()
     if b is None:
         return res
     par = parents[: K - 1].cpu().numpy()

@@ -18,6 +18,10 @@ one launch.  Boards, N = 2 .. 32; opt-in like everything here.
 full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_quench3d; csrc/mcq_quench3d.hip), N = 2 .. 32 and
 2 <= Q <= N^3 - 1: quench_queens, quench_queens_device, quench_queens_host.  The same labels apply -- the reference ships
 conflicts_for_queen (mcmc.py:185-226) and never calls it.
+
+hop_queens, hop_queens_device and hop_queens_host go on from a full_3d minimum (include/mcq.h: mcq_hop3d; csrc/mcq_hop3d.hip): a kick
+moves a few queens to free cells, the single-queen descent runs again, and the new minimum is kept when it is no worse; a whole run of
+hops is one launch.  queens_of_boards carries board placements into the cube.  Opt-in like everything here.
 """
 import numpy as np
 
@@ -434,3 +438,100 @@ def quench_queens(N, states, Q=None, max_passes=0, conflicts=True):
     res = quench_queens_device(N, torch.from_numpy(s).to(dev), Q=Q, max_passes=max_passes, conflicts=conflicts)
     torch.cuda.current_stream(dev).synchronize()
     return to_numpy(res)
+
+
+FIELDS_HOP3D = ("state", "energy_in", "energy_start", "energy_out", "best_energy", "best_hop", "best_state", "n_accepted", "n_improved", "n_moves",
+                "n_passes", "n_kicked", "energy_hist", "flags")
+
+
+def _block_hop3d(N, Q, n, n_hops, kick, slack, first_hop):
+    q = abi.Hop3d()
+    q.N, q.n_queens, q.n_chains, q.n_hops, q.first_hop = int(N), int(Q), int(n), int(n_hops), int(first_hop)
+    q.kick, q.slack = int(kick), int(slack)
+    return q
+
+
+def hop_queens_host(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, hist=False):
+    """mcq_hop3d_host: basin hopping of full_3d placements in the library's plain host code, NumPy in and out, no GPU.  Same result as
+    hop_queens, and it runs every shape (the kernel stops where a chain no longer fits the LDS: abi.hop3d_lds_bytes)."""
+    s = _host_queens(N, states, Q)
+    n = s.shape[0]
+    sd = _hop_seeds(seeds, n)
+    q = _block_hop3d(N, _queens_of(N, Q), n, n_hops, kick, slack, first_hop)
+    width = max(int(n_hops), 0) + 1
+    out = _host_outputs(q, s, abi.HOP3D_DTYPES, {"energy_hist": (n, width)}, () if hist else ("energy_hist",), like=("best_state",))
+    q.seeds, q.hist_stride = sd.ctypes.data, width
+    _lib.hop3d_host(q)
+    return out
+
+
+def hop_queens_device(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, hist=False, out=None, stream=None):
+    """mcq_hop3d_device on a torch uint8 tensor [n_chains][3 Q] or [n_chains][Q][3] of the current device (e.g. DeviceRun.t["best_state"]
+    of a full_3d run; Q=None means N^2) and an int32 or uint32 tensor `seeds` [n_chains] on the same device (the seeds' 32 bits, whatever
+    the sign), enqueued on `stream` (default: torch's current stream).  ONE kernel whatever n_hops is.  Asynchronous: nothing is copied
+    back and nothing synchronises.  `out` (optional) is the tensor the final placements go to; it may be `states` itself (in place),
+    default a new one.  Returns a dict of tensors with the fields of FIELDS_HOP3D: `state` and `best_state` uint8 like `states`;
+    `energy_in`, `energy_start`, `energy_out`, `best_energy`, `flags` int32[n_chains]; `best_hop`, `n_accepted`, `n_improved`, `n_moves`,
+    `n_passes`, `n_kicked` int64[n_chains]; and with hist=True `energy_hist` int32[n_chains][n_hops + 1]."""
+    import torch
+
+    n, Qn = _device_queens("hop_queens_device", N, states, Q)
+    dev = states.device
+    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
+            and tuple(seeds.shape) == (n,)):
+        raise ValueError(f"hop_queens_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = _block_hop3d(N, Qn, n, n_hops, kick, slack, first_hop)
+        width = max(int(n_hops), 0) + 1
+        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
+        for k, dt in abi.HOP3D_DTYPES.items():
+            if k != "energy_hist":
+                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+            elif hist:
+                res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
+        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
+        for k in abi.HOP3D_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.hop3d_device(q, st)
+    return res
+
+
+def hop_queens(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, hist=False):
+    """Basin hopping of full_3d placements on the GPU: `states` is uint8[n_chains][3 Q] or [n_chains][Q][3] (Q triples (i, j, k); Q=None
+    means N^2), bytes >= N are clamped to N - 1; `seeds` is uint32[n_chains].  Every placement first descends to a minimum under
+    single-queen moves (quench_queens with max_passes = 0); then n_hops times `kick` random queens are drawn with a random cell each and
+    move there when it is free, the descent runs again, and the new minimum stays when its energy is at most the old one + slack;
+    otherwise the placement goes back.  Returns a dict of NumPy arrays with the fields of FIELDS_HOP3D, `state` and `best_state`
+    uint8[n_chains][3 Q] (`energy_hist` only with hist=True); flags bit 0 (abi.HOP3D_REPEATED) marks an input with two queens in one
+    cell, which is recounted and handed back unmoved.  A run may be cut: feed `state` back in with first_hop = the hops done so far; the
+    figures of the pieces combine as hop_states says, n_passes in the place of n_pair_moves.  ValueError for what the library refuses
+    (N outside 2 .. 32, Q outside 2 .. N^3 - 1, no chain, kick outside 1 .. 1024, a negative n_hops, first_hop or slack, a chain above
+    the LDS of a workgroup: N = 32 runs up to Q = 23 520)."""
+    import torch
+
+    s = _host_queens(N, states, Q)
+    sd = _hop_seeds(seeds, s.shape[0])
+    if s.shape[0] == 0:
+        _lib.hop3d_host(_block_hop3d(N, _queens_of(N, Q), 0, n_hops, kick, slack, first_hop))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = hop_queens_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_hops, Q=Q, kick=kick, slack=slack,
+                            first_hop=first_hop, hist=hist)
+    torch.cuda.current_stream(dev).synchronize()
+    out = to_numpy(res)
+    out["state"], out["best_state"] = out["state"].reshape(s.shape), out["best_state"].reshape(s.shape)
+    return out
+
+
+def queens_of_boards(N, boards):
+    """Board placements as full_3d placements: heights uint8[n][N*N] (one board is taken as one chain; bytes >= N are clamped to N - 1)
+    -> the triples (i, j, h(i, j)) in row-major order of the columns, uint8[n][3 N^2].  The energy of the result in the cube is the
+    board's: two queens of different columns attack each other in the cube exactly when the board rule says so.  It carries board minima
+    into hop_queens, where the queens may leave their columns."""
+    N = int(N)
+    h = np.minimum(_host_states(N, boards), N - 1).astype(np.uint8)
+    out = np.empty((h.shape[0], N * N, 3), dtype=np.uint8)
+    c = np.arange(N * N)
+    out[:, :, 0], out[:, :, 1], out[:, :, 2] = (c // N).astype(np.uint8), (c % N).astype(np.uint8), h
+    return out.reshape(h.shape[0], 3 * N * N)
