@@ -1099,6 +1099,101 @@ int mcq_hop3d_device(const mcq_hop3d* q, void* hip_stream);
  * to the kernel bit for bit on every output. */
 int mcq_hop3d_host(const mcq_hop3d* q);
 
+/*
+ * Tabu search of board placements: every iteration takes the best admissible single-height move of a conflicting column, ALSO when
+ * it raises the energy, and forbids the way back for a while (csrc/mcq_tabu.hip) -- NOT a mode of the reference; never a default,
+ * like everything above that is labelled so.  The quenches stop on a minimum and the hops fall back onto the one they left; this
+ * block walks on from it.  Boards only.  The rule is integer-exact:
+ *   1. SETUP.  Every input byte is clamped to N - 1 first; a(c, k) and E are those of the mcq_quench rule, items 1 - 2.
+ *      delta(c, k) = a(c, k) - a(c, h(c)), the change of E when column c takes the height k.  Column c is CONFLICTING when
+ *      a(c, h(c)) > 0.  No local search is applied to the input; energy_in is its recount.
+ *   2. CHAIN STATE: the placement, a stamp T(c, k) >= 0 per column and height, the run's best energy B, and the iteration index.  A
+ *      call runs the iterations t = 0 .. n_iters - 1; iteration t has the GLOBAL index g = first_iter + t.  To begin with
+ *      T(c, k) = first_iter + tabu_in[c N + k], or 0 everywhere without tabu_in, and B = min(best_floor[r], energy_in), or energy_in
+ *      without best_floor.
+ *   3. RANDOM WORDS.  Iteration g draws one block (x0, x1, x2, x3) =
+ *        philox4x32-10(counter = (low 32 bits of g, high bits of g, 0, 0), key = (seeds[r], 7))
+ *      (key words 0 - 6 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop and mcq_hop3d).
+ *      o = floor(x0 N^3 / 2^32) is the tie offset, x1 gives the tenure's jitter (item 5), x2 and x3 are unused.
+ *   4. CANDIDATES: the (c, k) with c conflicting and k != h(c).  A candidate is TABU when T(c, k) > g.  It is ADMISSIBLE when it is
+ *      not tabu, or when E + delta(c, k) < B (aspiration).  The iteration takes the admissible candidate with the lexicographically
+ *      smallest (delta, rho), rho = (c N + k - o) mod N^3: of the candidates with the smallest delta the first one at or cyclically
+ *      behind a random offset, so ties carry no row-major bias.  With no admissible candidate the iteration moves nothing and counts
+ *      in n_stalled; E = 0 is one such case, forever (no column conflicts).
+ *   5. THE MOVE of the candidate (c, k), with F the number of conflicting columns BEFORE the move and h_old = h(c):
+ *        L = tenure + floor(x1 (tenure_rand + 1) / 2^32) + floor(tenure_conf F / 16)
+ *      then T(c, h_old) = g + 1 + L, h(c) = k and E += delta.  (The height left is tabu in the iterations g + 1 .. g + L.)  A move
+ *      with E + delta < B sets B, best_iter = t + 1 and the best placement.  best_iter is relative to the call; 0 means the input or an
+ *      earlier call.  Counters: n_moves; n_aspired, the moves whose candidate was tabu; n_uphill, the moves with delta > 0;
+ *      n_stalled.  All four are int64.
+ *   6. OUTPUTS.  energy_hist[r][0 .. n_iters] holds energy_in, then E after each iteration.  energy_out = E and state_out are
+ *      those behind the last iteration.  tabu_out[c N + k] = max(0, T(c, k) - (first_iter + n_iters)).  best_energy = B.
+ *      best_state is the best placement of THIS call: when no move of the call went below B it is the (clamped) input placement, and
+ *      best_energy = B <= energy_in says whether that placement has it.
+ * Bounds: tenure 0 .. MCQ_MAX_TABU_TENURE, tenure_rand 0 .. MCQ_MAX_TABU_TENURE_RAND, tenure_conf 0 .. MCQ_MAX_TABU_TENURE_CONF
+ * (F <= N^2 <= 1024), so that L <= 8192 + 4095 + 4096 < 2^14, and every tabu_out entry a run writes fits the uint16 of tabu_in /
+ * tabu_out (an entry carried from tabu_in only shrinks).  first_iter + n_iters < 2^63.
+ * Consequences:
+ *   (a) n_iters = 0 is the recount: state_out and best_state are the clamped input, energy_out = energy_in, best_energy = B,
+ *       tabu_out = tabu_in, every counter 0.
+ *   (b) a run cut into calls is the unbroken run on every output, when each call is fed state_out as state_in, tabu_out as tabu_in,
+ *       best_energy as best_floor and first_iter carried over: the four counters add up, the histories join (entry 0 of a later
+ *       call repeats the last entry of the one before), and best_iter / best_state are those of the LAST call with best_iter > 0,
+ *       its best_iter moved by the iterations before that call.
+ *   (c) an improving move (delta < 0) out of a placement with E = B is admissible whatever its stamp, by aspiration.  So whenever
+ *       at least one iteration ran behind best_iter (best_iter < n_iters; for best_iter = 0 also B = energy_in), best_state is a
+ *       single-move local minimum: mcq_quench moves nothing on it.
+ * N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS on the device and in host code alike.  Chains do not interact and a call reads all of a
+ * chain's inputs before it writes any of its outputs, so state_out may be state_in and tabu_out may be tabu_in; best_state may be
+ * neither state_in nor state_out.
+ *
+ * mcq_tabu_device keeps a chain in the LDS of one wavefront: the table a(c, k) as bytes in rows of 4 ((NP / 4) | 1) bytes, the stamps
+ * as uint16 in rows of 4 ((NP / 2) | 1) bytes, the heights and the best placement, NP = N rounded up to 4, 8, 12, 16, 24 or 32:
+ *   bytes = NP^2 (4 ((NP / 4) | 1) + 4 ((NP / 2) | 1) + 2),  108 544 at NP = 32 (one chain per compute unit), <= MCQ_MAX_TABU_LDS.
+ */
+#define MCQ_MAX_TABU_TENURE 8192
+#define MCQ_MAX_TABU_TENURE_RAND 4095
+#define MCQ_MAX_TABU_TENURE_CONF 64
+#define MCQ_MAX_TABU_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_tabu_device may take */
+typedef struct mcq_tabu {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS */
+    int32_t mode;           /* MCQ_MODE_BOARD; anything else is MCQ_EINVAL */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_iters;        /* >= 0; 0 = the recount */
+    int64_t first_iter;     /* >= 0: the global index of the call's first iteration; first_iter + n_iters < 2^63 */
+    int32_t tenure;         /* 0 .. MCQ_MAX_TABU_TENURE */
+    int32_t tenure_rand;    /* 0 .. MCQ_MAX_TABU_TENURE_RAND: the jitter is uniform on 0 .. tenure_rand */
+    int32_t tenure_conf;    /* 0 .. MCQ_MAX_TABU_TENURE_CONF: sixteenths of an iteration per conflicting column */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;     /* [n_chains][N*N]; may be state_in */
+    const uint16_t* tabu_in; /* optional [n_chains][N*N*N]: T(c, k) - first_iter, entry c N + k; NULL = nothing is tabu */
+    uint16_t* tabu_out;     /* optional [n_chains][N*N*N]; may be tabu_in */
+    const int32_t* best_floor; /* optional [n_chains]: the best energy of the calls before */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* best_energy;   /* optional [n_chains]: B */
+    int64_t* best_iter;     /* optional [n_chains]: 0 = no move of the call went below B, t + 1 = behind iteration t of the call */
+    uint8_t* best_state;    /* optional [n_chains][N*N]; neither state_in nor state_out */
+    int64_t* n_moves;       /* optional [n_chains] */
+    int64_t* n_aspired;     /* optional [n_chains]: moves whose candidate was tabu */
+    int64_t* n_uphill;      /* optional [n_chains]: moves with delta > 0 */
+    int64_t* n_stalled;     /* optional [n_chains]: iterations without an admissible candidate */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_iters */
+    int64_t hist_stride;    /* >= n_iters + 1 when energy_hist is given; not read otherwise */
+} mcq_tabu;
+
+/* the message of the last error of the calling thread from the two mcq_tabu_* calls below (they do not set mcq_last_error()) */
+const char* mcq_tabu_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_iters is; asynchronous: nothing is
+ * copied back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, mode other than
+ * board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative n_iters or first_iter, first_iter + n_iters >= 2^63, tenure,
+ * tenure_rand or tenure_conf outside their ranges, a NULL seeds, state_in or state_out, hist_stride below n_iters + 1 when energy_hist
+ * is given, a best_state that is state_in or state_out, and a chain above MCQ_MAX_TABU_LDS (no N in range is). */
+int mcq_tabu_device(const mcq_tabu* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+int mcq_tabu_host(const mcq_tabu* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

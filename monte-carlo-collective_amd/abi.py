@@ -306,6 +306,55 @@ def hop3d_lds_bytes(N, Q=None):
     return 4 * (32 + -(-cells // cpd) + -(-cells // 32) + 2 * ((Q + 1) // 2))
 
 
+MAX_TABU_TENURE = 8192         # include/mcq.h: MCQ_MAX_TABU_TENURE
+MAX_TABU_TENURE_RAND = 4095    # MCQ_MAX_TABU_TENURE_RAND
+MAX_TABU_TENURE_CONF = 64      # MCQ_MAX_TABU_TENURE_CONF
+MAX_TABU_LDS = 160 * 1024      # MCQ_MAX_TABU_LDS
+
+
+class Tabu(C.Structure):
+    """include/mcq.h: mcq_tabu -- tabu search of board placements: the best admissible move of a conflicting column, the way back forbidden for a while"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_iters", C.c_int64),
+        ("first_iter", C.c_int64),
+        ("tenure", C.c_int32),
+        ("tenure_rand", C.c_int32),
+        ("tenure_conf", C.c_int32),
+        ("seeds", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("tabu_in", C.c_void_p),
+        ("tabu_out", C.c_void_p),
+        ("best_floor", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_iter", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_aspired", C.c_void_p),
+        ("n_uphill", C.c_void_p),
+        ("n_stalled", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+    ]
+
+
+# the per-chain outputs of a tabu call besides the placements (state, best_state): field -> dtype ("energy_hist" has a row of n_iters + 1
+# per chain, "tabu_out" one of N^3)
+TABU_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "best_energy": np.int32, "best_iter": np.int64, "n_moves": np.int64,
+               "n_aspired": np.int64, "n_uphill": np.int64, "n_stalled": np.int64, "energy_hist": np.int32, "tabu_out": np.uint16}
+
+
+def tabu_lds_bytes(N):
+    """The bytes of LDS a chain of mcq_tabu_device takes (include/mcq.h, below the rule): table, stamps, heights and best placement."""
+    NP = next(p for p in (4, 8, 12, 16, 24, 32) if int(N) <= p)
+    return NP * NP * (4 * ((NP // 4) | 1) + 4 * ((NP // 2) | 1) + 2)
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

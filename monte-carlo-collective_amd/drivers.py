@@ -245,7 +245,7 @@ def write_best_heights(heights, N, path):
 
 def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.0, base_seed=42, init_mode="random",
                     out_dir="competition_results", runner=None, timestamp=None, resample_every=None, population=None, resample_seed=0, quench=False,
-                    heatbath_sweeps=None, heatbath_form="lines", hops=0, hop_kick=2):
+                    heatbath_sweeps=None, heatbath_form="lines", hops=0, hop_kick=2, tabu_iters=0, tabu_tenure=10):
     """competition.py:143-187: board chains with linear annealing beta_start -> beta_end, seeds base_seed + r; the board
     of the run with the lowest best energy is written to {out_dir}/best_heights_{N}_{timestamp}.txt.
     Returns (best energy, heights, path).
@@ -274,13 +274,24 @@ def run_competition(N=15, n_runs=10, n_steps=100000, beta_start=1.0, beta_end=3.
     best_state of the run with the lowest best_energy of the hops (the first such run).  The file has `_hopped` in its name, behind
     the suffix of `quench` if there is one, and the call returns FOUR values, (energy, heights, path, info), with info = {"hopped": K,
     "kick": hop_kick, "run": r, "energy_before": that run's best_energy, "energy_start": its energy behind the first descent,
-    "accepted", "improved", "best_hop"}; with `quench` set, info["quenched"] says which.  Boards up to N = 32."""
+    "accepted", "improved", "best_hop"}; with `quench` set, info["quenched"] says which.  Boards up to N = 32.
+
+    tabu_iters=K (not in the reference; 0 = nothing changes; refused together with hops): the best_state of every run goes through K
+    iterations of tabu search on the device instead (quench.tabu_states with tenure = `tabu_tenure`, no jitter; seeds base_seed + r, a
+    Philox key word of their own), and the board written is the walk's best_state of the run with the lowest best_energy (the first
+    such run).  The file has `_tabu` in its name, behind the suffix of `quench` if there is one, and the call returns FOUR values,
+    (energy, heights, path, info), with info = {"tabu": K, "tenure": tabu_tenure, "run": r, "energy_before": that run's best_energy,
+    "best_energy", "best_iter", "moves", "uphill", "aspired", "stalled"}; with `quench` set, info["quenched"] says which.  Boards up
+    to N = 32."""
     from . import quench as _quench
 
     _quench.check_mode(quench, N)
     _quench.check_hops(hops, hop_kick, N)
+    _quench.check_tabu(tabu_iters, tabu_tenure, hops, N)
 
     def _write(res, N, out_dir, timestamp, quench):
+        if tabu_iters:
+            return _write_tabu(res, N, out_dir, timestamp, quench, int(tabu_iters), int(tabu_tenure), ex.abi.seeds_for(base_seed, n_runs))
         if not hops:
             return _write_competition(res, N, out_dir, timestamp, quench)
         return _write_hopped(res, N, out_dir, timestamp, quench, int(hops), int(hop_kick), ex.abi.seeds_for(base_seed, n_runs))
@@ -354,6 +365,26 @@ def _write_hopped(res, N, out_dir, timestamp, quench, hops, hop_kick, seeds):
     if quench:
         info["quenched"] = "pairs" if quench == "pairs" else True
     return int(h["best_energy"][r]), heights, path, info
+
+
+def _write_tabu(res, N, out_dir, timestamp, quench, iters, tenure, seeds):
+    """run_competition with tabu_iters: the runs' best_state through the tabu walk, and the best of what it reaches to the file."""
+    import time
+
+    from . import quench as _quench
+
+    stamp = timestamp if timestamp is not None else time.strftime("%Y%m%d_%H%M%S")
+    w = _quench.tabu_states(N, np.asarray(res["best_state"]), seeds, iters, tenure=tenure)
+    r = int(np.argmin(w["best_energy"]))
+    heights = np.asarray(w["best_state"][r]).reshape(N, N)
+    suffix = "_quenched_pairs" if quench == "pairs" else "_quenched" if quench else ""
+    path = write_best_heights(heights, N, os.path.join(out_dir, f"best_heights_{N}_{stamp}{suffix}_tabu.txt"))
+    info = {"tabu": iters, "tenure": tenure, "run": r, "energy_before": int(res["best_energy"][r]), "best_energy": int(w["best_energy"][r]),
+            "best_iter": int(w["best_iter"][r]), "moves": int(w["n_moves"][r]), "uphill": int(w["n_uphill"][r]),
+            "aspired": int(w["n_aspired"][r]), "stalled": int(w["n_stalled"][r])}
+    if quench:
+        info["quenched"] = "pairs" if quench == "pairs" else True
+    return int(w["best_energy"][r]), heights, path, info
 
 
 def load_config(path="config.yaml"):

@@ -15,6 +15,11 @@ hop_states, hop_device and hop_host go on from a minimum (include/mcq.h: mcq_hop
 a few columns, the single-move or the pair-move descent again, and the new minimum kept when it is no worse.  A whole run of hops is
 one launch.  Boards, N = 2 .. 32; opt-in like everything here.
 
+tabu_states, tabu_device and tabu_host walk on from a minimum instead of falling back onto it (include/mcq.h: mcq_tabu;
+csrc/mcq_tabu.hip): tabu search, that is the best admissible single-height move of a conflicting column in every iteration, also when
+it raises the energy, with the height left forbidden for a while.  A whole run is one launch.  Boards, N = 2 .. 32; opt-in like
+everything here.
+
 full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_quench3d; csrc/mcq_quench3d.hip), N = 2 .. 32 and
 2 <= Q <= N^3 - 1: quench_queens, quench_queens_device, quench_queens_host.  The same labels apply -- the reference ships
 conflicts_for_queen (mcmc.py:185-226) and never calls it.
@@ -332,6 +337,147 @@ def check_hops(hops, hop_kick, N, board=True):
         raise ValueError(f"hops: N out of range [{abi.MIN_N}, {abi.MAX_N_QUENCH_PAIRS}]: {N}")
     if not 1 <= int(hop_kick) <= abi.MAX_HOP_KICK:
         raise ValueError(f"hop_kick out of range [1, {abi.MAX_HOP_KICK}]: {hop_kick}")
+
+
+FIELDS_TABU = ("state", "energy_in", "energy_out", "best_energy", "best_iter", "best_state", "n_moves", "n_aspired", "n_uphill", "n_stalled",
+               "energy_hist", "tabu_out")
+
+
+def _block_tabu(N, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter):
+    q = abi.Tabu()
+    q.N, q.mode, q.n_chains, q.n_iters, q.first_iter = int(N), abi.MODE_BOARD, int(n), int(n_iters), int(first_iter)
+    q.tenure, q.tenure_rand, q.tenure_conf = int(tenure), int(tenure_rand), int(tenure_conf)
+    return q
+
+
+def _tabu_skip(hist, tabu_out):
+    return (() if hist else ("energy_hist",)) + (() if tabu_out else ("tabu_out",))
+
+
+def tabu_host(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None, hist=False,
+              tabu_out=False):
+    """mcq_tabu_host: tabu search in the library's plain host code, NumPy in and out, no GPU.  Same result as tabu_states."""
+    s = _host_states(N, states)
+    n = s.shape[0]
+    sd = _hop_seeds(seeds, n)
+    q = _block_tabu(N, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
+    width, cube = max(int(n_iters), 0) + 1, s.shape[1] * max(int(N), 0)
+    out = _host_outputs(q, s, abi.TABU_DTYPES, {"energy_hist": (n, width), "tabu_out": (n, cube)}, _tabu_skip(hist, tabu_out), like=("best_state",))
+    q.seeds, q.hist_stride = sd.ctypes.data, width
+    keep = []
+    if tabu_in is not None:
+        keep.append(np.ascontiguousarray(tabu_in, dtype=np.uint16).reshape(-1))
+        if keep[-1].shape[0] != n * cube:
+            raise ValueError(f"tabu_in must be uint16[n_chains = {n}][N^3 = {cube}], got {np.shape(tabu_in)}")
+        q.tabu_in = keep[-1].ctypes.data
+    if best_floor is not None:
+        keep.append(np.ascontiguousarray(best_floor, dtype=np.int32).reshape(-1))
+        if keep[-1].shape[0] != n:
+            raise ValueError(f"best_floor must be int32[n_chains = {n}], got {np.shape(best_floor)}")
+        q.best_floor = keep[-1].ctypes.data
+    _lib.tabu_host(q)
+    return out
+
+
+def tabu_device(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None, hist=False,
+                tabu_out=False, out=None, stream=None):
+    """mcq_tabu_device on a torch uint8 tensor [n_chains][N*N] of the current device (e.g. DeviceRun.t["best_state"]) and an int32 or
+    uint32 tensor `seeds` [n_chains] on the same device, enqueued on `stream` (default: torch's current stream).  ONE kernel whatever
+    n_iters is.  Asynchronous: nothing is copied back and nothing synchronises.  `tabu_in` (optional) is an int16 or uint16 tensor
+    [n_chains][N^3] (the 16 bits, whatever the sign) and `best_floor` an int32 tensor [n_chains], both of an earlier call.  `out`
+    (optional) is the tensor the final placements go to; it may be `states` itself (in place), default a new one.  Returns a dict of
+    tensors with the fields of FIELDS_TABU: `state` and `best_state` uint8 like `states`; `energy_in`, `energy_out`, `best_energy`
+    int32[n_chains]; `best_iter`, `n_moves`, `n_aspired`, `n_uphill`, `n_stalled` int64[n_chains]; with hist=True `energy_hist`
+    int32[n_chains][n_iters + 1]; with tabu_out=True `tabu_out` int16[n_chains][N^3] (the uint16 stamps; to_numpy views them so)."""
+    import torch
+
+    n = _device_states("tabu_device", N, states)
+    dev = states.device
+    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
+            and tuple(seeds.shape) == (n,)):
+        raise ValueError(f"tabu_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
+    cube = int(states.shape[1]) * max(int(N), 0)
+    if tabu_in is not None and not (isinstance(tabu_in, torch.Tensor) and tabu_in.device == dev and tabu_in.is_contiguous() and tabu_in.numel() == n * cube
+                                    and tabu_in.dtype in (torch.int16, getattr(torch, "uint16", torch.int16))):
+        raise ValueError(f"tabu_device takes tabu_in as a contiguous int16 or uint16 tensor [n_chains = {n}][N^3 = {cube}] on the device of states")
+    if best_floor is not None and not (isinstance(best_floor, torch.Tensor) and best_floor.device == dev and best_floor.is_contiguous()
+                                       and best_floor.dtype == torch.int32 and tuple(best_floor.shape) == (n,)):
+        raise ValueError(f"tabu_device takes best_floor as a contiguous int32 tensor [n_chains = {n}] on the device of states")
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = _block_tabu(N, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
+        width = max(int(n_iters), 0) + 1
+        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
+        for k, dt in abi.TABU_DTYPES.items():
+            if k == "energy_hist":
+                if hist:
+                    res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
+            elif k == "tabu_out":
+                if tabu_out:
+                    res[k] = torch.empty((n, cube), dtype=torch.int16, device=dev)
+            else:
+                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
+        if tabu_in is not None:
+            q.tabu_in = tabu_in.data_ptr()
+        if best_floor is not None:
+            q.best_floor = best_floor.data_ptr()
+        for k in abi.TABU_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.tabu_device(q, st)
+    return res
+
+
+def tabu_to_numpy(res):
+    """The dict tabu_device returned, as NumPy arrays (tabu_out as uint16).  The stream must have passed the call."""
+    out = {k: t.cpu().numpy() for k, t in res.items()}
+    if "tabu_out" in out:
+        out["tabu_out"] = out["tabu_out"].view(np.uint16)
+    return out
+
+
+def tabu_states(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None, hist=False,
+                tabu_out=False):
+    """Tabu search of board placements on the GPU: `states` is uint8[n_chains][N*N] (one board of N*N heights is taken as one chain),
+    bytes >= N are clamped to N - 1; `seeds` is uint32[n_chains].  No descent runs first.  Each of the n_iters iterations takes, over the
+    columns whose queen is attacked, the single-height move with the smallest energy change -- a rise too; ties by a random rotation --
+    that is not tabu, or that leads below the best energy of the run, and the height it left is tabu for `tenure` iterations + a uniform
+    draw from 0 .. tenure_rand + tenure_conf / 16 per conflicting column.  Returns a dict of NumPy arrays with the fields of FIELDS_TABU
+    (`energy_hist` only with hist=True, `tabu_out` only with tabu_out=True); best_state is the best placement the call saw, the input
+    when best_iter = 0.  A run may be cut: feed `state` back in with first_iter = the iterations done so far, tabu_in = the tabu_out and
+    best_floor = the best_energy of the piece before; the counters of the pieces add up, and best_state / best_iter of the whole are
+    those of the LAST piece with best_iter > 0.  ValueError for what the library refuses (N outside 2 .. 32, no chain, tenure outside
+    0 .. 8192, tenure_rand outside 0 .. 4095, tenure_conf outside 0 .. 64, a negative n_iters or first_iter)."""
+    import torch
+
+    s = _host_states(N, states)
+    sd = _hop_seeds(seeds, s.shape[0])
+    if s.shape[0] == 0:
+        _lib.tabu_host(_block_tabu(N, 0, n_iters, tenure, tenure_rand, tenure_conf, first_iter))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ti = None if tabu_in is None else torch.from_numpy(np.ascontiguousarray(tabu_in, dtype=np.uint16).view(np.int16)).to(dev)
+    bf = None if best_floor is None else torch.from_numpy(np.ascontiguousarray(best_floor, dtype=np.int32)).to(dev)
+    res = tabu_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_iters, tenure=tenure, tenure_rand=tenure_rand,
+                      tenure_conf=tenure_conf, first_iter=first_iter, tabu_in=ti, best_floor=bf, hist=hist, tabu_out=tabu_out)
+    torch.cuda.current_stream(dev).synchronize()
+    return tabu_to_numpy(res)
+
+
+def check_tabu(tabu_iters, tabu_tenure, hops, N, board=True):
+    """ValueError for what the competition driver's `tabu_iters` hook does not take, before anything is launched."""
+    if int(tabu_iters) < 0:
+        raise ValueError(f"tabu_iters must be >= 0, got {tabu_iters}")
+    if int(tabu_iters) == 0:
+        return
+    if int(hops):
+        raise ValueError("tabu_iters and hops: one search behind the runs, not both")
+    if not board:
+        raise ValueError('tabu_iters: tabu search runs boards only (mcmc_type="board")')
+    if not abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH_PAIRS:
+        raise ValueError(f"tabu_iters: N out of range [{abi.MIN_N}, {abi.MAX_N_QUENCH_PAIRS}]: {N}")
+    if not 0 <= int(tabu_tenure) <= abi.MAX_TABU_TENURE:
+        raise ValueError(f"tabu_tenure out of range [0, {abi.MAX_TABU_TENURE}]: {tabu_tenure}")
 
 
 def check_mode(quench, N, board=True):
