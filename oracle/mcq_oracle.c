@@ -115,6 +115,13 @@ typedef struct {
     uint64_t words; /* words drawn so far (mcq_outputs.stream_words) */
 } rng_t;
 
+/* Side channel for the tests that craft a uniform next to exp (tests/near_tie_util.py): rng.words of every chain of the next runs, for both
+ * generators and without the 32-bit wrap -- mcq_outputs.stream_words stays 0 under Philox by contract (include/mcq.h).  The caller sets the
+ * array (n_chains entries) before a run and clears it afterwards; the workers write disjoint entries. */
+static uint64_t* g_words_out;
+
+void mcq_oracle_words_out(uint64_t* dst) { g_words_out = dst; }
+
 static void rng_seed(rng_t* s, int kind, uint32_t seed) {
     s->kind = kind;
     s->words = 0;
@@ -400,6 +407,7 @@ static int run_board_chain(const job_t* jb, int64_t r) {
     if (o->steps_to_best) o->steps_to_best[r] = best_step;
     if (o->n_accepted) o->n_accepted[r] = accepted;
     if (o->stream_words) o->stream_words[r] = p->rng == MCQ_RNG_MT19937_NUMPY ? (uint32_t)rng.words : 0u;
+    if (g_words_out) g_words_out[r] = rng.words;
     if (o->near_ties) o->near_ties[r] = ties;
     if (o->best_state)
         for (int c = 0; c < Q; c++) o->best_state[r * Q + c] = (uint8_t)best_h[c];
@@ -578,6 +586,7 @@ static int run_full_chain(const job_t* jb, int64_t r) {
     if (o->steps_to_best) o->steps_to_best[r] = best_step;
     if (o->n_accepted) o->n_accepted[r] = accepted;
     if (o->stream_words) o->stream_words[r] = p->rng == MCQ_RNG_MT19937_NUMPY ? (uint32_t)rng.words : 0u;
+    if (g_words_out) g_words_out[r] = rng.words;
     if (o->near_ties) o->near_ties[r] = ties;
     for (int c = 0; c < Q; c++) {
         if (o->best_state) {
@@ -736,6 +745,7 @@ static int run_board_chain_fast(const job_t* jb, int64_t r) {
     if (o->steps_to_best) o->steps_to_best[r] = best_step;
     if (o->n_accepted) o->n_accepted[r] = accepted;
     if (o->stream_words) o->stream_words[r] = p->rng == MCQ_RNG_MT19937_NUMPY ? (uint32_t)rng.words : 0u;
+    if (g_words_out) g_words_out[r] = rng.words;
     if (o->near_ties) o->near_ties[r] = ties;
     if (o->best_state)
         for (int c = 0; c < Q; c++) o->best_state[r * Q + c] = (uint8_t)best_h[c];
@@ -814,6 +824,7 @@ static int run_full_chain_fast(const job_t* jb, int64_t r) {
     if (o->steps_to_best) o->steps_to_best[r] = best_step;
     if (o->n_accepted) o->n_accepted[r] = accepted;
     if (o->stream_words) o->stream_words[r] = p->rng == MCQ_RNG_MT19937_NUMPY ? (uint32_t)rng.words : 0u;
+    if (g_words_out) g_words_out[r] = rng.words;
     if (o->near_ties) o->near_ties[r] = ties;
     for (int c = 0; c < Q; c++) {
         if (o->best_state) {
@@ -973,6 +984,7 @@ static void xchain_finish(xchain_t* c) {
     if (o->steps_to_best) o->steps_to_best[r] = c->best_step;
     if (o->n_accepted) o->n_accepted[r] = c->accepted;
     if (o->stream_words) o->stream_words[r] = c->p->rng == MCQ_RNG_MT19937_NUMPY ? (uint32_t)c->rng.words : 0u;
+    if (g_words_out) g_words_out[r] = c->rng.words;
     if (o->near_ties) o->near_ties[r] = c->ties;
     if (o->exchange_rung) o->exchange_rung[r] = c->rung;
     if (o->n_exchanges) o->n_exchanges[r] = c->n_exch;

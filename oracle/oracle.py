@@ -39,6 +39,8 @@ def lib():
         L.mcq_oracle_run_fast.restype = C.c_int
         L.mcq_oracle_run_fast.argtypes = [C.POINTER(abi.Params), C.c_void_p, C.POINTER(abi.Outputs), C.c_int]
         L.mcq_oracle_last_error.restype = C.c_char_p
+        L.mcq_oracle_words_out.restype = None
+        L.mcq_oracle_words_out.argtypes = [C.c_void_p]
         L.mcq_oracle_rng_stream.restype = C.c_int
         L.mcq_oracle_rng_stream.argtypes = [C.c_uint32, C.c_int, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
         L.mcq_oracle_philox_block.restype = C.c_int
@@ -49,10 +51,12 @@ def lib():
     return _lib
 
 
-def run(params, seeds, trace=True, states=True, n_threads=1, fast=False, host_beta=True):
+def run(params, seeds, trace=True, states=True, n_threads=1, fast=False, host_beta=True, words=False):
     """Run every chain on the CPU; returns {field: ndarray} shaped as abi.output_shapes().  fast=True: the line-counter
     variant (mcq_oracle_run_fast), same results.  host_beta=False: beta from the oracle's own libm evaluation of the schedule
-    instead of abi.beta_values (NumPy, the reference's arithmetic)."""
+    instead of abi.beta_values (NumPy, the reference's arithmetic).  words=True adds "rng_words", uint64[n_chains]: the 32-bit
+    words each chain drew, for both generators (the stream_words output is 0 under Philox by contract) -- no field of
+    mcq_outputs, a side channel of the oracle for the tests that look a uniform up in the stream."""
     seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
     assert seeds.shape == (params.n_chains,)
     arrays = {k: np.zeros(shape, dtype=abi.OUTPUT_DTYPES[k])
@@ -66,10 +70,17 @@ def run(params, seeds, trace=True, states=True, n_threads=1, fast=False, host_be
     if tab is not None:
         p.beta_table = tab.ctypes.data
     fn = lib().mcq_oracle_run_fast if fast else lib().mcq_oracle_run
-    rc = fn(C.byref(p), seeds.ctypes.data, C.byref(out), int(n_threads))
+    drawn = np.zeros(params.n_chains, dtype=np.uint64) if words else None
+    lib().mcq_oracle_words_out(drawn.ctypes.data if words else None)
+    try:
+        rc = fn(C.byref(p), seeds.ctypes.data, C.byref(out), int(n_threads))
+    finally:
+        lib().mcq_oracle_words_out(None)
     if rc != 0:
         msg = lib().mcq_oracle_last_error().decode()
         raise (ValueError if rc == abi.EINVAL else RuntimeError)(msg)
+    if words:
+        arrays["rng_words"] = drawn
     return arrays
 
 

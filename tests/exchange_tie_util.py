@@ -66,7 +66,7 @@ class XCase(nt.Case):
 
     def one_set(self, t):
         """Set t alone, as a case of its own (the crafting and the host tests run single sets)."""
-        sub = XCase(self.name, self.mode, self.N, self.lanes, self.R, self.K, n_sets=1, n_steps=self.n_steps, trace=True)
+        sub = XCase(self.name, self.mode, self.N, self.lanes, self.R, self.K, n_sets=1, n_steps=self.n_steps, trace=True, rng=self.rng)
         sub.ladder, sub._of = self.ladder, (self, t)
         return sub
 
@@ -87,8 +87,8 @@ class XCase(nt.Case):
 
 
 # One case per exchange kernel of the MT19937 stream (tests/test_exchange_ties_host.py asserts it), the board's unrolled N = 12 kernel a
-# second time without a trace.  No Philox case: with that stream the stream_words output is 0, so the place of an event's uniform in the
-# stream cannot be read off an oracle run.
+# second time without a trace.  The Philox stream has cases of its own below: its stream_words output is 0 by contract, so the place of an
+# event's uniform in the stream comes from the oracle's own word count (oracle.run(words=True)), for both generators.
 CASES = (
     XCase("x_board6_g2", "board", 6, 2, 16, 3, seed=3100, n_steps=449),
     XCase("x_board6_g4", "board", 6, 4, 16, 1, seed=3200, n_steps=317),
@@ -101,9 +101,30 @@ CASES = (
     XCase("x_full3d17_g16", "full_3d", 17, 16, 4, 5, ladder=(0.5, 2.0), seed=3900, n_steps=403),
     XCase("x_full3d6_g8", "full_3d", 6, 8, 8, 4, seed=4000, n_steps=309),
 )
-CASES_BY_NAME = {c.name: c for c in CASES}
+# One case per exchange kernel of the Philox stream (tests/test_philox_ties_host.py asserts it), with ladders of 2, 4, 8 and 16 rungs among them.
+PHILOX_CASES = (
+    XCase("px_board6_g2", "board", 6, 2, 16, 3, seed=8100, n_steps=449, rng="philox"),
+    XCase("px_board12_g4", "board", 12, 4, 4, 5, ladder=(0.5, 2.0), seed=8200, n_steps=395, rng="philox"),
+    XCase("px_board12_g8", "board", 12, 8, 8, 4, seed=8300, n_steps=351, rng="philox"),
+    XCase("px_board17_g16", "board", 17, 16, 4, 7, seed=8400, n_steps=470, rng="philox"),
+    XCase("px_full3d6_g4", "full_3d", 6, 4, 2, 2, ladder=(0.7, 1.3), seed=8500, n_steps=321, rng="philox"),
+    XCase("px_full3d12_g8", "full_3d", 12, 8, 8, 3, seed=8600, n_steps=338, rng="philox"),
+    XCase("px_full3d17_g16", "full_3d", 17, 16, 4, 1, seed=8700, n_steps=403, rng="philox"),
+)
+PHILOX_ROW = {
+    "px_board6_g2": (0, 2, 0, 0),
+    "px_board12_g4": (0, 4, 0, 0),
+    "px_board12_g8": (0, 8, 0, 0),
+    "px_board17_g16": (0, 16, 0, 0),
+    "px_full3d6_g4": (1, 4, 0, 0),
+    "px_full3d12_g8": (1, 8, 0, 0),
+    "px_full3d17_g16": (1, 16, 0, 0),
+}
+CASES_BY_NAME = {c.name: c for c in CASES + PHILOX_CASES}
 # the rows of SWEEP_TABLE with EXCH and without PHILOX, as (MODE, G, NT, NC)
 EXCHANGE_ROWS = {(0, 2, 0, 0), (0, 4, 3, 12), (0, 4, 0, 0), (0, 8, 0, 0), (0, 16, 0, 0), (1, 4, 0, 0), (1, 8, 3, 12), (1, 8, 0, 0), (1, 16, 0, 0)}
+# ... and with PHILOX
+PHILOX_EXCHANGE_ROWS = {(0, 2, 0, 0), (0, 4, 0, 0), (0, 8, 0, 0), (0, 16, 0, 0), (1, 4, 0, 0), (1, 8, 0, 0), (1, 16, 0, 0)}
 
 
 def check_ladder(case):
@@ -177,7 +198,7 @@ class _SetRuns:
     """Oracle runs of one set under its row, for the crafting."""
 
     def __init__(self, case, t, row):
-        self.sub, self.row, self.streams = case.one_set(t), row, nt._Streams()
+        self.sub, self.row, self.streams = case.one_set(t), row, nt._Streams(case.rng)
         self.seeds = self.sub.seeds()
         self.start = np.arange(case.set_chains) % case.R
 
@@ -188,7 +209,7 @@ class _SetRuns:
         tab = np.array(self.row[:n], dtype=np.float64).reshape(1, n)
         if last_beta is not None:
             tab[0, n - 1] = last_beta
-        return oracle.run(self.sub.params(tab, n_steps=n), self.seeds, states=False, fast=True)
+        return oracle.run(self.sub.params(tab, n_steps=n), self.seeds, states=False, fast=True, words=True)
 
     def uniform(self, chain, words):
         return nt.uniform_of(*self.streams.pair_before(int(self.seeds[chain]), int(words)))
@@ -212,7 +233,7 @@ def _try_swap(case, runs, s, before, request, tied):
         lt, lt1 = float(lad[t]), float(lad[t + 1])
         seen, res = None, first
         for _ in range(ROUNDS):
-            now = (int(res["final_energy"][a]) - int(res["final_energy"][b]), runs.uniform(a, res["stream_words"][a]))
+            now = (int(res["final_energy"][a]) - int(res["final_energy"][b]), runs.uniform(a, res["rng_words"][a]))
             if now == seen:  # beta(s) was derived from these very values, and they stand under it
                 beta, (dEab, u) = float(row[s]), now
                 prob = math.exp(swap_x(beta, lt, lt1, dEab))
@@ -245,7 +266,7 @@ def _try_step(case, runs, s, before, request, tied):
         rung = int(before["exchange_rung"][c])
         assert nt.accept_bit(probe, c, s), "beta = 0 accepts"
         dE = int(probe["energy_hist"][c, s + 1]) - int(probe["energy_hist"][c, s])
-        u = runs.uniform(c, int(probe["stream_words"][c]) - (2 if case.draws_at_event(rung, s) else 0))
+        u = runs.uniform(c, int(probe["rng_words"][c]) - (2 if case.draws_at_event(rung, s) else 0))
         l = float(case.ladder[rung])
         beta = _step_beta_for(spec, l, dE, u)
         if beta is not None:

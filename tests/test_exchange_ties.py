@@ -27,9 +27,9 @@ def _oracle(case, table):
     return _oracle_runs[case.name]
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_exchange_equals_the_oracle_next_to_exp(name):
-    """Every output is the oracle's, swap for swap and tie for tie, and the ties are the crafted ones, on the chains they were crafted for."""
+def exchange_equals_the_oracle_next_to_exp(name, row=None):
+    """Every output is the oracle's, swap for swap and tie for tie, and the ties are the crafted ones, on the chains they were crafted for.
+    `row` (tests/test_philox_ties.py): the row of SWEEP_TABLE the launch must take, as (MODE, G, NT, NC), on the stream the case names."""
     case = xt.CASES_BY_NAME[name]
     table, points = xt.crafted(name)
     xt.check_plan_was_met(case, points)
@@ -37,6 +37,9 @@ def test_exchange_equals_the_oracle_next_to_exp(name):
     want = _oracle(case, table)
     np.testing.assert_array_equal(want["near_ties"], crafted, err_msg=f"{name}: the oracle's own count (tests/test_exchange_ties_host.py)")
     assert int(want["n_exchanges"].sum()) > 0
+    v = mcq_amd._lib.sweep_variant(case.params(table))
+    assert v["EXCH"] and v["PHILOX"] == (case.rng == "philox") and (not case.lanes or v["G"] == case.lanes), (name, v)
+    assert row is None or tuple(int(v[k]) for k in ("MODE", "G", "NT", "NC")) == row, (name, v)
     for flags, how in ((0, "bracketed"), (abi.FLAG_EXACT_EXP, "exact exp")):
         what = f"{name} {how}"
         got, _ = mcq_amd._lib.run_host(case.params(table, flags=flags), seeds, trace=case.trace)
@@ -53,3 +56,8 @@ def test_exchange_equals_the_oracle_next_to_exp(name):
         if case.trace is True:
             for pt in xt.step_points(points):
                 assert nt.accept_bit(got, pt["chain"], pt["step"]) == int(pt["accept"]), (what, pt)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_exchange_equals_the_oracle_next_to_exp(name):
+    exchange_equals_the_oracle_next_to_exp(name)

@@ -25,8 +25,8 @@ def test_the_cases_run_every_exchange_kernel_of_the_mt19937_stream():
     assert rows == xt.EXCHANGE_ROWS, sorted(xt.EXCHANGE_ROWS - rows)
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_oracle_counts_the_crafted_ties_and_swaps_as_recomputed(name):
+def oracle_counts_the_crafted_ties_and_swaps_as_recomputed(name):
+    """(tests/test_philox_ties_host.py runs the same on the Philox cases.)"""
     case = xt.CASES_BY_NAME[name]
     table, points = xt.crafted(name)
     xt.check_plan_was_met(case, points)
@@ -64,6 +64,11 @@ def test_oracle_counts_the_crafted_ties_and_swaps_as_recomputed(name):
     assert int(control["near_ties"].sum()) == 0 and int(control["n_exchanges"].sum()) > 0, f"{name}: the uncrafted table ties by itself"
     ones = oracle.run(case.params(table, ladder=np.ones(case.R)), seeds, trace=case.trace, n_threads=4, fast=True)
     assert int(ones["near_ties"].sum()) == 0, f"{name}: a ladder of ones has exp(x) = 1 at every event: no swap can tie"
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_oracle_counts_the_crafted_ties_and_swaps_as_recomputed(name):
+    oracle_counts_the_crafted_ties_and_swaps_as_recomputed(name)
 
 
 def test_crafted_swap_uniforms_are_the_streams_words():

@@ -22,20 +22,6 @@ REDUCED_FIELDS = ("step_sum", "step_sumsq", "step_accepted", "step_count")
 _oracle_runs = {}
 
 
-def _reduced_from_trace(res, n_steps, n_sets):
-    """What the reduced trace holds (include/mcq.h: step_sum, step_sumsq, step_accepted, step_count per schedule set), from a full trace:
-    the oracle writes no reduced trace of its own."""
-    L, ex = res["hist_len"].astype(np.int64), res["steps_executed"].astype(np.int64)
-    h = res["energy_hist"][:, : n_steps + 1].astype(np.int64)
-    valid = np.arange(n_steps + 1)[None, :] < L[:, None]
-    hv = np.where(valid, h, 0)
-    bits = np.unpackbits(np.ascontiguousarray(res["accept_bits"]).view(np.uint8), axis=1, bitorder="little")[:, :n_steps].astype(np.int64)
-    bits *= np.arange(n_steps)[None, :] < ex[:, None]
-    acc = np.concatenate([np.zeros((len(L), 1), dtype=np.int64), bits], axis=1)
-    per_set = lambda a: a.reshape(n_sets, -1, n_steps + 1).sum(axis=1)  # noqa: E731
-    return {"step_sum": per_set(hv), "step_sumsq": per_set(hv * hv), "step_accepted": per_set(acc), "step_count": per_set(valid.astype(np.int64))}
-
-
 def _oracle(case, table):
     """The oracle's run of a case under its crafted table: computed once, shared, left unchanged.  For a reduced-trace case it is the run
     with the full trace plus the per-set sums of that trace."""
@@ -43,7 +29,7 @@ def _oracle(case, table):
         reduced = case.trace == "reduced"
         res = oracle.run(case.params(table, trace=True if reduced else "case"), case.seeds(), trace=True if reduced else case.trace, n_threads=8)
         if reduced:
-            res.update(_reduced_from_trace(res, case.n_steps, case.n_sets))
+            res.update(nt.reduced_from_trace(res, case.n_steps, case.n_sets))
         _oracle_runs[case.name] = res
     return _oracle_runs[case.name]
 
@@ -62,9 +48,9 @@ def _assert_equal(got, want, case, points, what):
         raise AssertionError(f"{e}\n{what}: {nt.first_difference(got, want, points, trace=case.trace)}") from None
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_sweep_equals_the_oracle_next_to_exp(name):
-    """Bracketed and with MCQ_FLAG_EXACT_EXP: both runs are the oracle's, tie for tie."""
+def sweep_equals_the_oracle_next_to_exp(name, row=None):
+    """Bracketed and with MCQ_FLAG_EXACT_EXP: both runs are the oracle's, tie for tie.  `row` (tests/test_philox_ties.py): the row of
+    SWEEP_TABLE the launch must take, as (MODE, G, PATIENCE, NT, REDUCED, NC), on the stream the case names."""
     case = nt.CASES_BY_NAME[name]
     table, points = nt.crafted(name)
     nt.check_plan_was_met(case, points)
@@ -74,6 +60,8 @@ def test_sweep_equals_the_oracle_next_to_exp(name):
     v = mcq_amd._lib.sweep_variant(case.params(table))
     assert v["PATIENCE"] == (case.patience is not None) and v["REDUCED"] == (case.trace == "reduced")
     assert v["SLIM"] == (name == "full3d10_g4") and v["WIDE"] == (name == "full3d40") and (not case.lanes or v["G"] == case.lanes)
+    assert v["PHILOX"] == (case.rng == "philox") and not v["EXCH"]
+    assert row is None or tuple(int(v[k]) for k in ("MODE", "G", "PATIENCE", "NT", "REDUCED", "NC")) == row, (name, v)
     for flags, how in ((0, "bracketed"), (abi.FLAG_EXACT_EXP, "exact exp")):
         got, _ = mcq_amd._lib.run_host(case.params(table, flags=flags), seeds, trace=case.trace)
         total = int(got["near_ties"].sum())
@@ -84,6 +72,11 @@ def test_sweep_equals_the_oracle_next_to_exp(name):
             for pt in points:
                 if pt["kind"] != "behind":
                     assert nt.accept_bit(got, pt["chain"], pt["step"]) == int(pt["accept"]), (name, how, pt)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_sweep_equals_the_oracle_next_to_exp(name):
+    sweep_equals_the_oracle_next_to_exp(name)
 
 
 def _cuts_around_a_tie(case, points):
