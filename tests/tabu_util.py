@@ -1,6 +1,8 @@
 """The tabu rule of include/mcq.h (mcq_tabu) restated in NumPy, from the text of the rule and from nothing else: a(c, k) is recounted
 naively before every iteration, the stamps T(c, k) are absolute Python-sized integers in an int64 array, and every iteration leaves a
-trace.  What mcq_tabu_host is compared with, and where the tests learn whether aspiration, the rotation of ties and the stall ran."""
+trace.  What mcq_tabu_host is compared with, and where the tests learn whether aspiration, the rotation of ties and the stall ran.
+Below the rule: the inputs that sleep until iteration 2^15 of a call with the window that restates them, and the boards at the ends of
+the kernel's packed key."""
 import functools
 
 import numpy as np
@@ -51,6 +53,7 @@ def tabu(N, board, seed, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first
     if tabu_in is not None:
         T = first_iter + np.asarray(tabu_in, dtype=np.int64).reshape(Q, N)
     cols, ks = np.indices((Q, N))
+    written = np.full((Q, N), -1, dtype=np.int64)  # the iteration whose move wrote T(c, k); -1: the stamp is the call's tabu_in
     a = table(N, h)
     e_in = int(a[np.arange(Q), h].sum()) // 2
     E = e_in
@@ -69,7 +72,8 @@ def tabu(N, board, seed, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first
         is_tabu = T > g
         adm = cand & (~is_tabu | (E + delta < B))
         F = int((now > 0).sum())
-        tr = {"candidates": int(cand.sum()), "F": F, "E": E, "o": o, "moved": False}
+        held = cand & is_tabu & ~(E + delta < B) & (written >= 0)  # candidates that a stamp of an earlier move of this call keeps out
+        tr = {"candidates": int(cand.sum()), "F": F, "E": E, "o": o, "moved": False, "g": g, "held_since": int(written[held].min()) if held.any() else None}
         if not adm.any():
             n["n_stalled"] += 1
         else:
@@ -86,6 +90,7 @@ def tabu(N, board, seed, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first
             n["n_aspired"] += int(is_tabu[c, k])
             n["n_uphill"] += int(dmin > 0)
             T[c, h[c]] = g + 1 + L
+            written[c, h[c]] = g
             h[c] = k
             E += dmin
             if E < B:
@@ -184,3 +189,67 @@ def counters_cover(got):
         after += bool(len(rises) and len(news) and news[-1] > rises[0])
     return {"aspired": int(got["n_aspired"].sum()), "uphill": int(got["n_uphill"].sum()),
             "stall_above_0": int(((got["n_stalled"] > 0) & (hist.min(axis=1) > 0)).sum()), "best_after_uphill": after}
+
+
+# Inputs that sleep, then wake across the move of the kernel's stamp base.  With every entry of a chain tabu and best_floor = 0 the rule
+# admits nothing: the chain stalls, and its placement and absolute stamps stay as they are until the first stamp expires.  So the run
+# from iteration W on is, by consequence (b), the run with first_iter = W, tabu_in - W and best_floor = 0, and only that window has to
+# be restated, while a kernel has to run all of it in one call and move its base at iteration REBASE of the call.
+REBASE = 1 << 15
+LONGEST = dict(tenure=8192, tenure_rand=4095, tenure_conf=64)
+SLEEP_EXPIRIES = {"spread": (32700, 32841, 32700), "edge": (32767, 32771, 32760)}  # variant -> [low, high) of tabu_in, and W
+
+
+def sleeping(N, n, seed, variant):
+    """(tabu_in, W): n chains whose every entry is tabu until it expires around iteration 2^15 of the call, none before W.  "spread":
+    expiries U[32700, 32840]; "edge": only 32767, 32768, 32769 and 32770, so everything wakes within three iterations of the move."""
+    lo, hi, W = SLEEP_EXPIRIES[variant]
+    return np.random.RandomState(seed).randint(lo, hi, size=(n, N ** 3)).astype(np.uint16), W
+
+
+def wake(N, states, seeds, n_iters, tabu_in, W, **kw):
+    """The outputs of the sleeping run of n_iters >= W iterations from iteration 0, restated over [W, n_iters) alone; `trace` holds the
+    window (trace[r][i] is iteration W + i)."""
+    n = len(states)
+    win = tabu_many(N, states, seeds, n_iters - W, first_iter=W, tabu_in=np.asarray(tabu_in).astype(np.int64) - W, best_floor=np.zeros(n, dtype=np.int64), **kw)
+    out = dict(win)
+    out["n_stalled"] = win["n_stalled"] + W
+    out["best_iter"] = np.where(win["best_iter"] > 0, win["best_iter"] + W, 0)
+    out["energy_hist"] = np.concatenate([np.repeat(win["energy_hist"][:, :1], W, axis=1), win["energy_hist"]], axis=1)
+    return out
+
+
+def assert_asleep(got, W, what):
+    """The premise of `wake`, on the outputs of code that ran the whole call: nothing moved before iteration W."""
+    hist = np.asarray(got["energy_hist"]).astype(np.int64)
+    assert (hist[:, : W + 1] == hist[:, :1]).all() and (np.asarray(got["n_stalled"]) >= W).all(), f"{what}: a chain moved before iteration {W}"
+    assert (np.asarray(got["n_moves"]) + np.asarray(got["n_stalled"]) == hist.shape[1] - 1).all(), what
+
+
+def wake_cover(traces, mark=REBASE):
+    """Of the windows' traces: moves before and from iteration `mark` on, and the iterations from `mark` on in which a stamp written
+    before `mark` keeps a candidate out."""
+    n = {"moves_before": 0, "moves_after": 0, "held_across": 0}
+    for chain in traces:
+        for tr in chain:
+            n["moves_before"] += tr["moved"] and tr["g"] < mark
+            n["moves_after"] += tr["moved"] and tr["g"] >= mark
+            n["held_across"] += tr["g"] >= mark and tr["held_since"] is not None and tr["held_since"] < mark
+    return n
+
+
+# Boards at the ends of the kernel's packed key (delta + 124) << 15 | rho
+def flat_board(N):
+    """Every queen at height 0: each column is attacked by all its aligned columns, and the first moves take delta = -max a(c, k)."""
+    return np.zeros((1, N * N), dtype=np.uint8)
+
+
+def uphill_board(N):
+    """(board, tabu_in): flat but for the centre column at height N / 2, and every entry tabu for 50 iterations except (centre, 0).
+    Under best_floor = 0 the only admissible move puts the centre queen back among all its aligned columns: the largest rise."""
+    b = flat_board(N)
+    centre = (N // 2) * N + N // 2
+    b[0, centre] = N // 2
+    tin = np.full((1, N * N, N), 50, dtype=np.uint16)
+    tin[0, centre, 0] = 0
+    return b, tin.reshape(1, -1)

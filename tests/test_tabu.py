@@ -1,9 +1,12 @@
 """GPU: the tabu kernel (mcq_tabu_device) against the library's host code (mcq_tabu_host) bit for bit on every output, histories and
-tabu_out included, at both ends of every instantiation; long runs in which the stamp base moves twice, whole and cut at the move; a cut
-run at N = 12; in place; a stream of its own; 4 096 heat-bath placements through the invariants of the rule; and the run_competition
-hook against the composed calls.  Before a group of comparisons counts it must hold aspired and uphill moves, a stall above E = 0 and a
-new best behind a rise (from the host code's counters and histories), and winners that are not the row-major first of their ties and a
-wrapped rho (from the restatement of tests/tabu_util.py on the first iterations of every first chain)."""
+tabu_out included, at both ends of every instantiation, and chain 0 of every such case against the restatement of tests/tabu_util.py
+over the whole run; sleeping runs that wake at iteration 2^15 of one call, at both ends of the instantiations 12 to 32, whole, cut one
+iteration before the base moves and at it, ending at it, and through 2^16 iterations up to N = 13; long runs in which the stamp base
+moves twice with moves throughout (N = 4, 5, 9, 13); the top of the 16-bit stamp range and tabu_in at the contract's ends; the largest
+fall and the largest rise the packed key can hold; first_iter on both sides of 2^32; a cut run at N = 12; in place; a stream of its
+own; 4 096 heat-bath placements through the invariants of the rule; and the run_competition hook against the composed calls.  Before a
+comparison counts its coverage is asserted, from the restatement's traces (tests/tabu_cases.py) or, where stated, from the host code's
+counters and histories; none is computed from the kernel's outputs."""
 import functools
 import os
 
@@ -13,68 +16,27 @@ import pytest
 import mcq_amd
 from tests import quench_util as qu
 from tests import resume_util as ru
+from tests import tabu_cases as tc
 from tests import tabu_util as tu
 
 abi = mcq_amd.abi
 quench = mcq_amd.quench
 pytestmark = pytest.mark.gpu
 
-# the instantiations are padded N = 4, 8, 12, 16, 24, 32: both ends of each
-GROUPS = {4: (2, 4), 8: (5, 8), 12: (9, 12), 16: (13, 16), 24: (17, 24), 32: (25, 32)}
-DEEP_FROM = 17     # from this N on the comparisons start deep in a walk: a short run from a random board only descends
-DEEP_ITERS = 2500
-DEEP_TENURE = dict(tenure=8, tenure_rand=4, tenure_conf=2)
-TRACED = 40        # iterations of every first chain that the restatement follows
-ALL = dict(hist=True, tabu_out=True)
-
-
-def _iters(N):
-    return 300 if N < DEEP_FROM else 200
-
-
-def _stamps(N, n, seed, hold):
-    """Random stamps of up to 40 iterations; chain 0 has every entry tabu for `hold` iterations."""
-    tin = np.random.RandomState(seed).randint(0, 41, size=(n, N ** 3)).astype(np.uint16)
-    tin[0] = hold
-    return tin
-
-
-@functools.lru_cache(maxsize=None)
-def _deep(N):
-    """3 boards of N >= DEEP_FROM behind DEEP_ITERS iterations of the host code, with their stamps and best energies: inputs only."""
-    s = qu.random_boards(N, 3, 100 * N, over=True)
-    return quench.tabu_host(N, s, abi.seeds_for(900 + N, 3), DEEP_ITERS, tabu_out=True, **DEEP_TENURE)
-
-
-def _cases(N):
-    """(boards, seeds, keywords) of the comparisons at N: every chain count; tenure = 8192 at N <= 3 and a start with every entry of a
-    chain tabu under a floor of 0 are the stalls, random stamps the aspiration; at N >= DEEP_FROM the walk goes on from _deep."""
-    if N >= DEEP_FROM:
-        d = _deep(N)
-        deep = dict(first_iter=DEEP_ITERS, tabu_in=d["tabu_out"], best_floor=d["best_energy"], **DEEP_TENURE)
-        s = qu.random_boards(N, 3, 100 * N + 3, over=True)
-        floor = np.full(3, 1 << 30, dtype=np.int32)
-        floor[0] = 0
-        return ((d["state"][:1], abi.seeds_for(900 + N, 1), {k: (v[:1] if isinstance(v, np.ndarray) else v) for k, v in deep.items()}),
-                (d["state"], abi.seeds_for(900 + N, 3), deep),
-                (s, abi.seeds_for(500 + N, 3), dict(tenure=3, tenure_rand=5, tabu_in=_stamps(N, 3, N, 50), best_floor=floor)))
-    floor = np.full(5, 1 << 30, dtype=np.int32)
-    floor[0] = 0
-    return ((qu.random_boards(N, 1, 100 * N + 1, over=True), abi.seeds_for(500 + N, 1), dict(tenure=8192 if N <= 3 else N // 2 + 1, tenure_rand=3)),
-            (qu.random_boards(N, 5, 100 * N + 5, over=True), abi.seeds_for(510 + N, 5), dict(tenure=2, tenure_rand=5, tenure_conf=8, tabu_in=_stamps(N, 5, N, 100),
-                                                                                               best_floor=floor)),
-            (qu.random_boards(N, 65, 100 * N + 65, over=True), abi.seeds_for(520 + N, 65), dict(tenure=N, tenure_rand=N, tenure_conf=4)))
+GROUPS = tc.GROUPS
+ALL = tc.ALL
+_iters, _stamps = tc.iters, tc.stamps
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(N):
-    """[(boards, seeds, keywords, the host code's result, the restatement's first iterations of chain 0)] at N; computed once and shared."""
+    """[(boards, seeds, keywords, the host code's result, the restatement's whole run of chain 0)] at N; computed once and shared."""
     out = []
-    for s, seeds, kw in _cases(N):
+    for i, (s, seeds, kw) in enumerate(tc.cases(N)):
         want = quench.tabu_host(N, s, seeds, _iters(N), **ALL, **kw)
-        one = {k: (v[0] if isinstance(v, np.ndarray) else v) for k, v in kw.items()}
-        traced = tu.tabu(N, s[0], int(seeds[0]), TRACED, **one)
-        np.testing.assert_array_equal(traced["energy_hist"], want["energy_hist"][0, : TRACED + 1])  # a run's beginning is a run
+        traced = tc.restated(N, i, 0)
+        assert len(traced["trace"]) == _iters(N)
+        tu.assert_equal(tc.row(want, 0), traced, f"N={N} case {i}: host code against the restatement")
         out.append((s, seeds, kw, want, traced))
     return out
 
@@ -96,11 +58,12 @@ def _check_coverage(NP):
 def test_kernel_equals_the_host_code(NP):
     print(NP, _check_coverage(NP))
     for N in GROUPS[NP]:
-        for s, seeds, kw, want, _ in _reference(N):
+        for s, seeds, kw, want, traced in _reference(N):
             assert int(s.max()) >= N or s.shape[0] < 65  # clamped bytes among the random inputs
             got = quench.tabu_states(N, s, seeds, _iters(N), **ALL, **kw)
             what = f"N={N} chains={s.shape[0]}"
             tu.assert_equal(got, want, what)
+            tu.assert_equal(tc.row(got, 0), traced, what + ": chain 0 against the restatement")
             assert set(got) == set(quench.FIELDS_TABU)
             for k, dt in abi.TABU_DTYPES.items():
                 assert got[k].dtype == dt, k
@@ -109,14 +72,15 @@ def test_kernel_equals_the_host_code(NP):
             tu.assert_equal(slim, want, what + " without the optional outputs", fields=[k for k in tu.FIELDS if k in slim])
 
 
-@pytest.mark.parametrize("N", (4, 5))
+@pytest.mark.parametrize("N", (4, 5, 9, 13))
 def test_the_stamp_base_moves_twice(N):
     """70 000 iterations under the longest tenure: the base of the kernel's 16-bit stamps moves at iterations 32 768 and 65 536, and
     stamps of 32 767 + 1 + 8192 + 4095 are written before a move.  Then the same run cut at 32 767 + 2 + rest, tabu_out carried: the
-    second piece starts one iteration before the whole run's base moves, with the stamps the first piece left."""
+    second piece starts one iteration before the whole run's base moves, with the stamps the first piece left.  At N = 9 and 13 (the
+    instantiations 12 and 16) with tenure_conf = 64 on top."""
     n, iters = 5, 70000
     s, seeds = qu.random_boards(N, n, 30 + N, over=True), abi.seeds_for(40 + N, n)
-    kw = dict(tenure=8192, tenure_rand=4095)
+    kw = dict(tenure=8192, tenure_rand=4095) if N <= 5 else dict(tu.LONGEST)
     want = quench.tabu_host(N, s, seeds, iters, **ALL, **kw)
     assert (want["n_stalled"] > 0).all() and (want["n_moves"] > 100).all() and want["n_uphill"].sum() > 0
     # moves on both sides of both marks, and stamps alive at the end
@@ -127,6 +91,110 @@ def test_the_stamp_base_moves_twice(N):
     parts = tu.run_cut(quench.tabu_states, N, s, seeds, (32767, 2, iters - 32769), **ALL, **kw)
     tu.assert_equal(tu.merge(parts), want, f"N={N}: 32 767 + 2 + rest")
     assert int(parts[0]["tabu_out"].max()) > 8192  # stamps that the second piece needs
+
+
+@pytest.mark.parametrize("variant", tc.VARIANTS)
+@pytest.mark.parametrize("N", sorted(tc.SLEEP_CHAINS))
+def test_the_kernel_wakes_at_iteration_2_15(N, variant):
+    """Sleeping runs (tests/tabu_util.py) at both ends of the instantiations 12, 16, 24 and 32: every stamp expires around iteration
+    2^15 of ONE call, so the kernel moves its base with stamps of the longest tenure alive, written just before, and with stamps that
+    expire exactly at, one before and one or two after the move.  The kernel equals the host code and the restated window on every
+    output; so do the run cut one iteration before the move and at it, and a call that ends at the move."""
+    print(N, variant, tc.check_wakes(N, variant))
+    s, seeds, tin, W, want = tc.sleep_case(N, variant)
+    kw = tc.sleep_kw(N, variant)
+    host = quench.tabu_host(N, s, seeds, tc.SLEEP_ITERS, **ALL, **kw)
+    tu.assert_asleep(host, W, f"N={N} {variant}")
+    tu.assert_equal(host, want, f"N={N} {variant}: host code against the restated window")
+    got = quench.tabu_states(N, s, seeds, tc.SLEEP_ITERS, **ALL, **kw)
+    tu.assert_equal(got, host, f"N={N} {variant}: {tc.SLEEP_ITERS} iterations")
+    tu.assert_equal(got, want, f"N={N} {variant}: against the restated window")
+    for cuts in ((tu.REBASE - 1, 2, tc.SLEEP_ITERS - tu.REBASE - 1), (tu.REBASE, tc.SLEEP_ITERS - tu.REBASE)):
+        parts = tu.run_cut(quench.tabu_states, N, s, seeds, cuts, **ALL, **kw)
+        tu.assert_equal(tu.merge(parts), want, f"N={N} {variant}: cut {cuts}")
+    ends = tc.sleep_case(N, variant, tu.REBASE)[4]  # the call that ends where the base would move: the restated window is [W, 2^15)
+    assert int(ends["tabu_out"].max()) > 8192
+    tu.assert_equal(quench.tabu_states(N, s, seeds, tu.REBASE, **ALL, **kw), ends, f"N={N} {variant}: {tu.REBASE} iterations")
+    if N <= 13:  # the second move of the base, against the host code (tests/test_tabu_host.py: its cut at 2^15 is the whole)
+        twice = quench.tabu_host(N, s, seeds, 2 * tu.REBASE, **ALL, **kw)
+        assert (np.diff(twice["energy_hist"].astype(np.int64)[:, tc.SLEEP_ITERS:], axis=1) != 0).any(axis=1).all() and int(twice["tabu_out"].max()) > 0
+        tu.assert_equal(quench.tabu_states(N, s, seeds, 2 * tu.REBASE, **ALL, **kw), twice, f"N={N} {variant}: {2 * tu.REBASE} iterations")
+
+
+@pytest.mark.parametrize("N", (25, 32))
+def test_the_top_of_the_stamp_range(N):
+    """tabu_in with 65535, 65534, 32769, 32768, 32767, 1 and 0 among stamps that expire around iteration 2^15, nearly every column
+    conflicting and the three tenure terms at their maxima: the moves just before the base moves write base-relative stamps within
+    1024 of the largest there can be (at N = 32: of 2^15 + 2^14), and the base then moves under them and under the 65535s."""
+    top, bound = tc.top_stamp(N)
+    assert top >= bound and (N != 32 or bound == (1 << 15) + (1 << 14) - 1024), (top, bound)
+    s, seeds, tin, W, want = tc.top_case(N)
+    kw = dict(tabu_in=tin, best_floor=np.zeros(1, dtype=np.int32), **tu.LONGEST)
+    host = quench.tabu_host(N, s, seeds, tc.TOP_ITERS, **ALL, **kw)
+    tu.assert_asleep(host, W, f"N={N}")
+    tu.assert_equal(host, want, f"N={N}: host code against the restated window")
+    moved = np.flatnonzero(np.diff(host["energy_hist"][0].astype(np.int64)) != 0)
+    assert ((moved >= W) & (moved < tu.REBASE)).sum() >= 60 and (moved >= tu.REBASE).sum() >= 300 and int(host["tabu_out"].max()) == 65535 - tc.TOP_ITERS
+    got = quench.tabu_states(N, s, seeds, tc.TOP_ITERS, **ALL, **kw)
+    tu.assert_equal(got, host, f"N={N}: the top of the stamp range")
+    tu.assert_equal(got, want, f"N={N}: against the restated window")
+
+
+def test_no_iterations_is_the_recount():
+    """tabu_in over the whole uint16 range goes through a call of no iterations as it is."""
+    for N, n in ((5, 4), (13, 2), (32, 1)):
+        s = qu.random_boards(N, n, 9 + N, over=True)
+        tin = np.random.RandomState(N).randint(0, 1 << 16, size=(n, N ** 3)).astype(np.uint16)
+        tin[:, :4] = (65535, 32768, 32767, 0)
+        seeds = abi.seeds_for(1, n)
+        got = quench.tabu_states(N, s, seeds, 0, tenure=5, first_iter=(1 << 40) + 3, tabu_in=tin, **ALL)
+        clamped = np.minimum(s, N - 1)
+        np.testing.assert_array_equal(got["state"], clamped)
+        np.testing.assert_array_equal(got["best_state"], clamped)
+        np.testing.assert_array_equal(got["tabu_out"], tin)
+        e = np.array([qu.energy(N, b) for b in s])
+        for k in ("energy_in", "energy_out", "best_energy"):
+            np.testing.assert_array_equal(got[k], e, err_msg=k)
+        np.testing.assert_array_equal(got["energy_hist"], e[:, None])
+        for k in tu.COUNTERS + ("best_iter",):
+            assert not got[k].any(), k
+        tu.assert_equal(got, quench.tabu_host(N, s, seeds, 0, tenure=5, first_iter=(1 << 40) + 3, tabu_in=tin, **ALL), f"N={N}: n_iters=0")
+        floor = e - np.arange(n, dtype=np.int64) + 1  # above, at and below the recount
+        np.testing.assert_array_equal(quench.tabu_states(N, s, seeds, 0, best_floor=floor.astype(np.int32))["best_energy"], np.minimum(floor, e))
+
+
+@pytest.mark.parametrize("N", tc.KEY_N)
+def test_the_largest_fall_and_the_largest_rise(N):
+    """The ends of the key (delta + 124) << 15 | rho: delta = -max a(c, k) from the flat board and +(max a(c, k) - 3) back onto it,
+    -123 and +120 at N = 32, with ties among such candidates."""
+    for kind in ("flat", "uphill"):
+        print(N, kind, tc.check_key(N, kind))
+        b, seeds, kw, want = tc.key_case(N, kind)
+        host = quench.tabu_host(N, b, seeds, tc.KEY_ITERS[kind], **ALL, **kw)
+        tu.assert_equal(host, want, f"N={N} {kind}: host code against the restatement")
+        got = quench.tabu_states(N, b, seeds, tc.KEY_ITERS[kind], **ALL, **kw)
+        tu.assert_equal(got, want, f"N={N} {kind}")
+        tu.assert_equal(got, host, f"N={N} {kind}: against the host code")
+
+
+@pytest.mark.parametrize("N,n,first", tc.WORD_CASES)
+def test_first_iter_on_both_sides_of_2_32(N, n, first):
+    """The second word of the Philox counter is not 0: whole and cut 7 + 1 + 52 against the restatement and the host code, and not
+    the run that a counter without its high word would give."""
+    s, seeds, want = tc.word_case(N, n, first)
+    low = tc.low_word_hist(tu.tabu_many, N, s, seeds, first)
+    assert (want["energy_hist"] != low).any(axis=1).all(), "the high word decides nothing in these runs"
+    kw = dict(first_iter=first, **tc.WORD_TENURE)
+    host = quench.tabu_host(N, s, seeds, tc.WORD_ITERS, **ALL, **kw)
+    tu.assert_equal(host, want, f"N={N} first_iter={first}: host code against the restatement")
+    got = quench.tabu_states(N, s, seeds, tc.WORD_ITERS, **ALL, **kw)
+    tu.assert_equal(got, want, f"N={N} first_iter={first}")
+    tu.assert_equal(got, host, f"N={N} first_iter={first}: against the host code")
+    parts = tu.run_cut(quench.tabu_states, N, s, seeds, (7, 1, 52), **ALL, **kw)
+    tu.assert_equal(tu.merge(parts), want, f"N={N} first_iter={first}: cut")
+    dropped = tc.low_word_hist(quench.tabu_states, N, s, seeds, first, **ALL)
+    np.testing.assert_array_equal(dropped, low)
+    assert (dropped != got["energy_hist"]).any(axis=1).all()
 
 
 def test_a_cut_run_is_the_unbroken_run():

@@ -1,8 +1,11 @@
 """CPU-only: tabu search in host code (mcq_tabu_host) against its NumPy restatement (tests/tabu_util.py) on every output, histories and
 tabu_out included; that the compared runs hold aspired and uphill moves, winners that are not the row-major first of their ties, a
-wrapped rho, a stall above E = 0 and a new best behind a rise (from the restatement's traces, before a group counts); n_iters = 0; a run
-cut 7 + 1 + rest; best_state against the quench; the two tenure terms alone; first_iter on both sides of 2^32; every refusal; the
-layout of the mcq_tabu block."""
+wrapped rho, a stall above E = 0 and a new best behind a rise (from the restatement's traces, before a group counts); the whole runs of
+the first, middle and last chain of every case that tests/test_tabu.py puts to the kernel; sleeping runs that wake at iteration 2^15
+of a call (what the kernel's move of its stamp base is held by), the sleep itself restated once, and the three confusions of the stamps
+next to that iteration shown to change a history; the top of the stamp range; the largest fall and rise; n_iters = 0; a run cut 7 + 1 +
+rest; best_state against the quench; the two tenure terms alone; first_iter on both sides of 2^32; every refusal; the layout of the
+mcq_tabu block."""
 import ctypes
 import functools
 import os
@@ -15,6 +18,7 @@ import pytest
 import mcq_amd
 from tests import heatbath_util as hb
 from tests import quench_util as qu
+from tests import tabu_cases as tc
 from tests import tabu_util as tu
 
 abi = mcq_amd.abi
@@ -113,6 +117,97 @@ def test_host_code_equals_the_restatement_at_large_n(N):
         got = quench.tabu_host(N, b, seeds, 60, hist=True, tabu_out=True, **kw)
         tu.assert_equal(got, want, f"N={N} case {i}")
         _check_shapes(got, 1, N, 60)
+
+
+@pytest.mark.parametrize("N", sorted(N for pair in tc.GROUPS.values() for N in pair))
+def test_host_code_equals_the_restatement_on_whole_runs(N):
+    """The comparisons of tests/test_tabu.py: the first, the middle and the last chain of every case, every iteration, every output.
+    The kernel is compared with the restatement on chain 0 and with the host code on the others."""
+    for i, (s, seeds, kw) in enumerate(tc.cases(N)):
+        got = quench.tabu_host(N, s, seeds, tc.iters(N), **tc.ALL, **kw)
+        for r in sorted({0, s.shape[0] // 2, s.shape[0] - 1}):
+            tu.assert_equal(tc.row(got, r), tc.restated(N, i, r), f"N={N} case {i} chain {r}")
+
+
+def test_a_sleeping_run_stalls_until_its_window():
+    """The premise of tu.wake as a fact of the rule: the restatement through a whole sleeping run, every iteration from 0, is the run
+    that tu.wake puts together from the window."""
+    N, variant = 9, "edge"
+    s, seeds, tin, W, want = tc.sleep_case(N, variant)
+    whole = tu.tabu(N, s[0], int(seeds[0]), tc.SLEEP_ITERS, tabu_in=tin[0], best_floor=0, **tu.LONGEST)
+    assert not any(tr["moved"] for tr in whole["trace"][:W]) and sum(tr["moved"] for tr in whole["trace"]) > 100
+    tu.assert_equal(whole, tc.row(want, 0), f"N={N}: the whole sleeping run")
+    assert [tr["moved"] for tr in whole["trace"][W:]] == [tr["moved"] for tr in want["trace"][0]]
+
+
+@pytest.mark.parametrize("variant", tc.VARIANTS)
+@pytest.mark.parametrize("N", sorted(tc.SLEEP_CHAINS))
+def test_host_code_wakes_at_iteration_2_15(N, variant):
+    """Sleeping runs of 2^15 + 332 iterations under the longest tenure, and calls of exactly 2^15 and 2^15 + 1 iterations: the host
+    code (which has no stamp base) equals the restated window on every output.  What the kernel is compared with in tests/test_tabu.py."""
+    print(N, variant, tc.check_wakes(N, variant))
+    s, seeds, tin, W, want = tc.sleep_case(N, variant, more=True)
+    kw = tc.sleep_kw(N, variant, more=True)
+    assert len(s) in (2, 3)
+    for n_iters in (tc.SLEEP_ITERS, tu.REBASE, tu.REBASE + 1):
+        got = quench.tabu_host(N, s, seeds, n_iters, **tc.ALL, **kw)
+        tu.assert_asleep(got, W, f"N={N} {variant} {n_iters}")
+        tu.assert_equal(got, tc.sleep_case(N, variant, n_iters, more=True)[4], f"N={N} {variant}: {n_iters} iterations")
+    assert int(tc.sleep_case(N, variant, tu.REBASE, more=True)[4]["tabu_out"].max()) > 8192  # stamps alive at the end of the call that ends at the mark
+    if N <= 13:  # 2^16 iterations: the cut at 2^15 carries tabu_out over what would be a base's second move
+        whole = quench.tabu_host(N, s, seeds, 2 * tu.REBASE, **tc.ALL, **kw)
+        tu.assert_equal(tu.merge(tu.run_cut(quench.tabu_host, N, s, seeds, (tu.REBASE, tu.REBASE), **tc.ALL, **kw)), whole, f"N={N} {variant}: 2^15 + 2^15")
+        np.testing.assert_array_equal(whole["energy_hist"][:, : tc.SLEEP_ITERS + 1], want["energy_hist"])
+        assert (np.diff(whole["energy_hist"].astype(np.int64)[:, tc.SLEEP_ITERS:], axis=1) != 0).any(axis=1).all() and int(whole["tabu_out"].max()) > 0
+
+
+@pytest.mark.parametrize("NP", (12, 16, 24, 32))
+def test_the_stamps_next_to_the_mark_decide(NP):
+    """The edge variant cut at iteration 2^15 with tabu_out carried: the stamps that a base moved by 2^15 must hold.  A stamp equal to
+    2^15 reads 0 (free), 2^15 + 1 reads 1 (tabu for one more iteration), 2^15 + 2 reads 2; each of the three confusions, put into the
+    carried stamps, changes a history of this group, so a kernel that commits one cannot equal the restatement."""
+    changed = dict.fromkeys(("1 -> 0", "2^15: 0 -> 1", "2 -> 1"), 0)
+    for N in tc.GROUPS[NP]:
+        s, seeds, tin, W, want = tc.sleep_case(N, "edge")
+        n, rest = len(s), 40
+        head = tu.tabu_many(N, s, seeds, tu.REBASE - W, first_iter=W, tabu_in=tin.astype(np.int64) - W, best_floor=np.zeros(n, dtype=np.int64), **tu.LONGEST)
+        carried = head["tabu_out"]
+        assert set(np.unique(carried[carried < 3])) == {0, 1, 2} and ((carried == 0) & (tin == tu.REBASE)).any()
+
+        def tail(stamps):
+            return tu.tabu_many(N, head["state"], seeds, rest, first_iter=tu.REBASE, tabu_in=stamps, best_floor=np.zeros(n, dtype=np.int64), **tu.LONGEST)["energy_hist"]
+
+        np.testing.assert_array_equal(tail(carried), want["energy_hist"][:, tu.REBASE : tu.REBASE + rest + 1])
+        for what, stamps in (("1 -> 0", np.where(carried == 1, 0, carried)), ("2^15: 0 -> 1", np.where((carried == 0) & (tin == tu.REBASE), 1, carried)),
+                             ("2 -> 1", np.where(carried == 2, 1, carried))):
+            changed[what] += int((tail(stamps) != tail(carried)).any(axis=1).sum())
+    print(NP, changed)
+    assert all(changed.values()), f"group {NP}: {changed}"
+
+
+@pytest.mark.parametrize("N", (25, 32))
+def test_the_top_of_the_stamp_range(N):
+    """tabu_in with 65535, 65534, 32769, 32768, 32767, 1 and 0 among stamps that expire around iteration 2^15, most columns
+    conflicting, the three tenure terms at their maxima: the moves just before iteration 2^15 write the largest stamps there are."""
+    top, bound = tc.top_stamp(N)
+    assert top >= bound and (N != 32 or bound == (1 << 15) + (1 << 14) - 1024), (top, bound)
+    s, seeds, tin, W, want = tc.top_case(N)
+    assert all(int((tin == v).sum()) >= 20 for v in tc.TOP_VALUES + (0, 1)) and min(tr["F"] for tr in want["trace"][0]) > 3 * N * N // 4
+    got = quench.tabu_host(N, s, seeds, tc.TOP_ITERS, tabu_in=tin, best_floor=np.zeros(1, dtype=np.int32), **tc.ALL, **tu.LONGEST)
+    tu.assert_asleep(got, W, f"N={N}")
+    tu.assert_equal(got, want, f"N={N}: the top of the stamp range")
+    assert int(got["tabu_out"].max()) == 65535 - tc.TOP_ITERS
+
+
+@pytest.mark.parametrize("N", tc.KEY_N)
+def test_the_largest_fall_and_the_largest_rise(N):
+    """delta = -max a(c, k) from the flat board and +(max a(c, k) - 3) back onto it: at N = 32, -123 and +120."""
+    for kind in ("flat", "uphill"):
+        a_max, deltas = tc.check_key(N, kind)
+        print(N, kind, a_max, deltas)
+        b, seeds, kw, want = tc.key_case(N, kind)
+        tu.assert_equal(quench.tabu_host(N, b, seeds, tc.KEY_ITERS[kind], **tc.ALL, **kw), want, f"N={N} {kind}")
+    assert N != 32 or (tc.check_key(32, "flat")[1][0], tc.check_key(32, "uphill")[1][0]) == (-123, 120)
 
 
 def test_no_iterations_is_the_recount():
