@@ -1194,6 +1194,104 @@ int mcq_tabu_device(const mcq_tabu* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
 int mcq_tabu_host(const mcq_tabu* q);
 
+/*
+ * Tabu search of full_3d placements: every iteration takes the best admissible move of a conflicting queen to a free cell of the
+ * cube, ALSO when it raises the energy, and forbids the cell it left for a while (csrc/mcq_tabu3d.hip) -- NOT a mode of the reference;
+ * never a default, like everything above that is labelled so.  mcq_tabu above keeps refusing full_3d: a queen here has N^3 targets
+ * and the stamps belong to cells, and this block has its own entry points.  The rule is integer-exact:
+ *   1. SETUP.  The placement (Q triples of bytes, 3 Q bytes per chain), the clamping to N - 1, REPEATED, a(q, t) and E are those of
+ *      the mcq_quench3d rule, items 1 - 2.  N = 2 .. MCQ_MAX_N_QUENCH3D and 2 <= Q <= N^3 - 1 (n_queens = 0 means N^2).  Queen q is
+ *      CONFLICTING when a(q, pos(q)) > 0; a cell is FREE when it holds no queen; delta(q, t) = a(q, t) - a(q, pos(q)), the change of
+ *      E when queen q moves to the free cell t.  No local search is applied to the input; energy_in is its recount.
+ *   2. CHAIN STATE: the placement, a stamp T(t) >= 0 per cell of the cube, the run's best energy B, and the iteration index.  A
+ *      call runs the iterations t = 0 .. n_iters - 1; iteration t has the GLOBAL index g = first_iter + t.  To begin with
+ *      T(t) = first_iter + tabu_in[t], or 0 everywhere without tabu_in, t the cell index i N^2 + j N + k, and
+ *      B = min(best_floor[r], energy_in), or energy_in without best_floor.
+ *   3. RANDOM WORDS.  Iteration g draws one block (x0, x1, x2, x3) =
+ *        philox4x32-10(counter = (low 32 bits of g, high bits of g, 0, 0), key = (seeds[r], 8))
+ *      (key words 0 - 7 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d and mcq_tabu).
+ *      o_q = floor(x0 Q / 2^32) and o_t = floor(x2 N^3 / 2^32) are the tie offsets, x1 gives the tenure's jitter (item 5), x3 is
+ *      unused.
+ *   4. CANDIDATES: the pairs (q, t) with q conflicting and t free.  A candidate is TABU when T(t) > g: the stamp belongs to the
+ *      cell, whichever queen would enter it.  It is ADMISSIBLE when it is not tabu, or when E + delta(q, t) < B (aspiration).  The
+ *      iteration takes the admissible candidate with the lexicographically smallest (delta, rho_q, rho_t),
+ *      rho_q = (q - o_q) mod Q and rho_t = (t - o_t) mod N^3.  With no admissible candidate the iteration moves nothing and counts
+ *      in n_stalled; E = 0 is one such case, forever (no queen conflicts).
+ *   5. THE MOVE of the candidate (q, t), with F the number of conflicting queens BEFORE the move and p = pos(q):
+ *        L = min(MCQ_MAX_TABU3D_SPAN, tenure + floor(x1 (tenure_rand + 1) / 2^32) + floor(tenure_conf F / 16))
+ *      then T(p) = g + 1 + L, pos(q) = t and E += delta.  (The cell left is tabu in the iterations g + 1 .. g + L.)  F may reach
+ *      N^3 - 1 here, so L is capped and not the parameters.  A move with E + delta < B sets B, best_iter = t + 1 and the best
+ *      placement.  Counters: n_moves; n_aspired, the moves whose candidate was tabu; n_uphill, the moves with delta > 0; n_stalled.
+ *      All four are int64.
+ *   6. OUTPUTS.  energy_hist, energy_out, state_out, best_energy, best_state and best_iter are exactly as in the mcq_tabu rule,
+ *      item 6.  tabu_out[t] = max(0, T(t) - (first_iter + n_iters)).
+ *   7. a REPEATED input (two queens in one cell after clamping) sets bit 0 of flags (MCQ_TABU3D_REPEATED) and is handed back
+ *      unmoved: state_out and best_state are the clamped input, energy_in = energy_out = best_energy = the recount (a shared cell
+ *      counts as an attacking pair; best_floor is not looked at), every counter and best_iter are 0, energy_hist[0 .. n_iters] all
+ *      hold the recount, and tabu_out = tabu_in, or zeros without it.  No output of the rule is such a placement.
+ * Bounds: tenure, tenure_rand and tenure_conf as under mcq_tabu; L <= MCQ_MAX_TABU3D_SPAN = 2^14 - 1, so that every tabu_out entry a
+ * run writes fits the uint16 of tabu_in / tabu_out.  first_iter + n_iters < 2^63.
+ * Consequences:
+ *   (a) n_iters = 0 is the recount: state_out and best_state are the clamped input, energy_out = energy_in, best_energy = B,
+ *       tabu_out = tabu_in, every counter 0.
+ *   (b) a run cut into calls is the unbroken run on every output, when each call is fed state_out as state_in, tabu_out as tabu_in,
+ *       best_energy as best_floor and first_iter carried over; the figures of the pieces combine as under mcq_tabu (b).
+ *   (c) a queen that does not conflict cannot improve, and an improving move out of a placement with E = B is admissible whatever
+ *       its stamp, by aspiration.  So whenever at least one iteration ran behind best_iter (best_iter < n_iters; for best_iter = 0
+ *       also B = energy_in), mcq_quench3d moves nothing on best_state.
+ * Chains do not interact and a call reads all of a chain's inputs before it writes any of its outputs, so state_out may be state_in
+ * and tabu_out may be tabu_in; best_state may be neither state_in nor state_out.
+ *
+ * mcq_tabu3d_device keeps a chain in the LDS of one workgroup: 32 dwords, the stamps (16 bits per cell), the field (one byte per cell
+ * to N = 19, 16 bits beyond), the occupancy bitmap and the queens (16 bits each), each array rounded up to a dword:
+ *   bytes = 4 (32 + ceil(N^3 / 2) + ceil(N^3 / (4 or 2)) + ceil(N^3 / 32) + ceil(Q / 2)) <= MCQ_MAX_TABU3D_LDS.
+ * Every Q = N^2 fits (137 344 bytes at N = 32); at N = 32 the largest Q is 14 272.  mcq_tabu3d_host runs every shape.
+ */
+#define MCQ_MAX_TABU3D_SPAN 16383 /* 2^14 - 1: the longest tenure L of a move */
+#define MCQ_MAX_TABU3D_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_tabu3d_device may take */
+#define MCQ_TABU3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) input hold the same cell; nothing was moved */
+typedef struct mcq_tabu3d {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t n_queens;       /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_iters;        /* >= 0; 0 = the recount */
+    int64_t first_iter;     /* >= 0: the global index of the call's first iteration; first_iter + n_iters < 2^63 */
+    int32_t tenure;         /* 0 .. MCQ_MAX_TABU_TENURE */
+    int32_t tenure_rand;    /* 0 .. MCQ_MAX_TABU_TENURE_RAND: the jitter is uniform on 0 .. tenure_rand */
+    int32_t tenure_conf;    /* 0 .. MCQ_MAX_TABU_TENURE_CONF: sixteenths of an iteration per conflicting queen */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;     /* [n_chains][Q][3]; may be state_in */
+    const uint16_t* tabu_in; /* optional [n_chains][N*N*N]: T(t) - first_iter, entry i N^2 + j N + k; NULL = nothing is tabu */
+    uint16_t* tabu_out;     /* optional [n_chains][N*N*N]; may be tabu_in */
+    const int32_t* best_floor; /* optional [n_chains]: the best energy of the calls before */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* best_energy;   /* optional [n_chains]: B */
+    int64_t* best_iter;     /* optional [n_chains]: 0 = no move of the call went below B, t + 1 = behind iteration t of the call */
+    uint8_t* best_state;    /* optional [n_chains][Q][3]; neither state_in nor state_out */
+    int64_t* n_moves;       /* optional [n_chains] */
+    int64_t* n_aspired;     /* optional [n_chains]: moves whose candidate was tabu */
+    int64_t* n_uphill;      /* optional [n_chains]: moves with delta > 0 */
+    int64_t* n_stalled;     /* optional [n_chains]: iterations without an admissible candidate */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_iters */
+    int64_t hist_stride;    /* >= n_iters + 1 when energy_hist is given; not read otherwise */
+    int32_t* flags;         /* optional [n_chains]: MCQ_TABU3D_* */
+} mcq_tabu3d;
+
+/* the message of the last error of the calling thread from the two mcq_tabu3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_tabu3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_iters is; asynchronous: nothing is
+ * copied back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, N outside
+ * 2 .. 32 (33 .. 64 named as this build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, a negative
+ * n_iters or first_iter, first_iter + n_iters >= 2^63, tenure, tenure_rand or tenure_conf outside their ranges, a NULL seeds, state_in
+ * or state_out, hist_stride below n_iters + 1 when energy_hist is given, a best_state that is state_in or state_out, and any (N, Q)
+ * whose chain exceeds MCQ_MAX_TABU3D_LDS (the message names N, Q and the bytes). */
+int mcq_tabu3d_device(const mcq_tabu3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, for every shape (no LDS here), otherwise the same refusals; needs no GPU.  Equal
+ * to the kernel bit for bit on every output. */
+int mcq_tabu3d_host(const mcq_tabu3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

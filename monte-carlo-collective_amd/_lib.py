@@ -234,6 +234,11 @@ def lib():
         L.mcq_tabu_device.argtypes = [C.POINTER(abi.Tabu), C.c_void_p]
         L.mcq_tabu_host.restype = C.c_int
         L.mcq_tabu_host.argtypes = [C.POINTER(abi.Tabu)]
+        L.mcq_tabu3d_last_error.restype = C.c_char_p
+        L.mcq_tabu3d_device.restype = C.c_int
+        L.mcq_tabu3d_device.argtypes = [C.POINTER(abi.Tabu3d), C.c_void_p]
+        L.mcq_tabu3d_host.restype = C.c_int
+        L.mcq_tabu3d_host.argtypes = [C.POINTER(abi.Tabu3d)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -399,6 +404,28 @@ def tabu_host(q):
 def tabu_device(q, stream):
     """mcq_tabu_device on a filled abi.Tabu block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_tabu(lib().mcq_tabu_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_tabu3d(rc):
+    """_check for the mcq_tabu3d_* calls, which keep their own message (mcq_tabu3d_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_tabu3d_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def tabu3d_host(q):
+    """mcq_tabu3d_host on a filled abi.Tabu3d block of HOST pointers.  Pure host code, no GPU."""
+    _check_tabu3d(lib().mcq_tabu3d_host(C.byref(q)))
+
+
+def tabu3d_device(q, stream):
+    """mcq_tabu3d_device on a filled abi.Tabu3d block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_tabu3d(lib().mcq_tabu3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def _check_quench3d(rc):

@@ -355,6 +355,56 @@ def tabu_lds_bytes(N):
     return NP * NP * (4 * ((NP // 4) | 1) + 4 * ((NP // 2) | 1) + 2)
 
 
+MAX_TABU3D_SPAN = (1 << 14) - 1  # include/mcq.h: MCQ_MAX_TABU3D_SPAN
+MAX_TABU3D_LDS = 160 * 1024    # MCQ_MAX_TABU3D_LDS
+TABU3D_REPEATED = 1            # MCQ_TABU3D_REPEATED: bit 0 of flags
+
+
+class Tabu3d(C.Structure):
+    """include/mcq.h: mcq_tabu3d -- tabu search of full_3d placements: the best admissible move of a conflicting queen, the cell left forbidden for a while"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_iters", C.c_int64),
+        ("first_iter", C.c_int64),
+        ("tenure", C.c_int32),
+        ("tenure_rand", C.c_int32),
+        ("tenure_conf", C.c_int32),
+        ("seeds", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("tabu_in", C.c_void_p),
+        ("tabu_out", C.c_void_p),
+        ("best_floor", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_iter", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_aspired", C.c_void_p),
+        ("n_uphill", C.c_void_p),
+        ("n_stalled", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d tabu call besides the placements (state, best_state): field -> dtype ("energy_hist" has a row of
+# n_iters + 1 per chain, "tabu_out" one of N^3)
+TABU3D_DTYPES = dict(TABU_DTYPES, flags=np.int32)
+
+
+def tabu3d_lds_bytes(N, Q=None):
+    """The bytes of LDS a chain of mcq_tabu3d_device takes (include/mcq.h, below the rule): it runs what stays within MAX_TABU3D_LDS."""
+    N = int(N)
+    Q = N * N if Q is None or int(Q) == 0 else int(Q)
+    cells, cpd = N ** 3, 4 if N <= 19 else 2
+    return 4 * (32 + -(-cells // 2) + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2)
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

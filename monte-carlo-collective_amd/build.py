@@ -30,6 +30,9 @@ HOP3D_SOURCES = [os.path.join(CSRC, "mcq_hop3d.hip")]
 # tabu search of board placements, a best-admissible-move walk over the table of the board hops with a stamp per entry: an eighth list,
 # as tests pin the seven above; compiled into the same library
 TABU_SOURCES = [os.path.join(CSRC, "mcq_tabu.hip")]
+# tabu search of full_3d placements, a best-admissible-move walk over one attack field with a stamp per cell: a ninth list, as tests pin
+# the eight above; compiled into the same library
+TABU3D_SOURCES = [os.path.join(CSRC, "mcq_tabu3d.hip")]
 # what the sources include: the C-ABI; the chain record of the sweep and the resume kernels; the attack field of the full_3d files;
 # what the four files outside the sweep (the quenches and the heat baths) share beyond it; the lane helpers of the board heat-bath column
 # update, which the tempered sweep shares
@@ -52,14 +55,14 @@ def stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    return any(os.path.getmtime(f) > t for f in SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + HEADERS)
+    return any(os.path.getmtime(f) > t for f in SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + TABU3D_SOURCES + HEADERS)
 
 
 def build(force=False, verbose=False):
     """Compile the HIP kernels + C-ABI for gfx950; returns the path of the shared library."""
     if not force and not stale():
         return SO
-    cmd = [hipcc()] + FLAGS + ["-o", SO] + SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES
+    cmd = [hipcc()] + FLAGS + ["-o", SO] + SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + TABU3D_SOURCES
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)

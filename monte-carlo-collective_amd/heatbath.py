@@ -255,7 +255,7 @@ def check(n_chains, n_sweeps, resample_every, population=None):
 
 
 def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=None, population=None, resample_seed=0, quench=False, trace=False,
-                    mcmc_type="board", Q=None, form="lines", hops=0, hop_kick=2):
+                    mcmc_type="board", Q=None, form="lines", hops=0, hop_kick=2, tabu_iters=0, tabu_tenure=10, tabu_tenure_rand=0):
     """Every chain of `seeds` for n_sweeps heat-bath sweeps under one beta schedule, beta of sweep s = abi.beta_values(schedule_params,
     n_sweeps)[s] (the reference's schedules, evaluated per sweep instead of per step).
 
@@ -283,6 +283,12 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
     `hopped_state`, `hopped_energy` (the best of the hops: best_state and best_energy of that call), `hop_accepted`, `hop_improved` and
     `hop_best_hop`.  Boards refuse it: their hops are drivers.run_competition(hops=...).
 
+    tabu_iters = K > 0 (full_3d only; default 0: nothing changes; refused together with hops) sends best_state -- the quenched one
+    with quench=True -- through K iterations of quench.tabu_queens_device with tenure = tabu_tenure and tenure_rand = tabu_tenure_rand
+    on the same stream, seeded with the seeds of the run: `res` gains `tabu_state`, `tabu_energy` (the best of the walk: best_state
+    and best_energy of that call), `tabu_best_iter` and `tabu_moves`.  Boards refuse it: their walk is
+    drivers.run_competition(tabu_iters=...).
+
     form (one of FORMS, default "lines") is the kernel every board segment runs through (heatbath_device's `form`; the results do not
     depend on it); "counters" needs N <= 16, and full_3d placements have the one form "lines".
 
@@ -307,6 +313,8 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         raise ValueError('hops: anneal_heatbath hops full_3d placements only (mcmc_type="full_3d"); boards hop through run_competition(hops=...)')
     if hops and not 1 <= int(hop_kick) <= abi.MAX_HOP_KICK:
         raise ValueError(f"hop_kick out of range [1, {abi.MAX_HOP_KICK}]: {hop_kick}")
+    tabu_iters = int(tabu_iters)
+    _quench.check_tabu_queens(tabu_iters, tabu_tenure, tabu_tenure_rand, hops, N, Q, board=mcmc_type != "full_3d")
 
     n_sweeps = int(n_sweeps)
     if n_sweeps < 0:
@@ -366,7 +374,7 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         dseeds = torch.from_numpy(seeds.view(np.int32).copy()).to(dev)
         dtab = device_table(beta, dev)  # the whole run's rows, uploaded once; a segment reads its slice
         hist = i32(n, n_sweeps + 1) if trace else None
-        quenched = hopped = None
+        quenched = hopped = walked = None
         if b is None:
             seg = sweep(N, state, dseeds, dtab if n_sweeps else [], first_sweep=0, out=state, trace=trace, stream=st)  # one call, in place
             hist = seg.get("energy_hist")
@@ -418,6 +426,9 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         if hops:  # behind the quench when there is one, whose placements it takes; same stream, nothing waited for
             hopped = _quench.hop_queens_device(N, quenched["state"] if quenched is not None else acc["best_state"], dseeds, hops, Q=Qn,
                                                kick=int(hop_kick), stream=st)
+        if tabu_iters:  # in the place of the hops: behind the quench when there is one; same stream, nothing waited for
+            walked = _quench.tabu_queens_device(N, quenched["state"] if quenched is not None else acc["best_state"], dseeds, tabu_iters, Q=Qn,
+                                                tenure=int(tabu_tenure), tenure_rand=int(tabu_tenure_rand), stream=st)
         st.synchronize()
 
     res = {"initial_energy": e0.cpu().numpy(), "final_energy": e1.cpu().numpy(), "final_state": state.cpu().numpy(),
@@ -433,6 +444,9 @@ def anneal_heatbath(N, n_sweeps, init, schedule_params, seeds, resample_every=No
         res["hopped_state"], res["hopped_energy"] = hopped["best_state"].cpu().numpy(), hopped["best_energy"].cpu().numpy()
         res["hop_accepted"], res["hop_improved"] = hopped["n_accepted"].cpu().numpy(), hopped["n_improved"].cpu().numpy()
         res["hop_best_hop"] = hopped["best_hop"].cpu().numpy()
+    if walked is not None:
+        res["tabu_state"], res["tabu_energy"] = walked["best_state"].cpu().numpy(), walked["best_energy"].cpu().numpy()
+        res["tabu_best_iter"], res["tabu_moves"] = walked["best_iter"].cpu().numpy(), walked["n_moves"].cpu().numpy()
     if b is None:
         return res
     par = parents[: K - 1].cpu().numpy()

@@ -27,6 +27,10 @@ conflicts_for_queen (mcmc.py:185-226) and never calls it.
 hop_queens, hop_queens_device and hop_queens_host go on from a full_3d minimum (include/mcq.h: mcq_hop3d; csrc/mcq_hop3d.hip): a kick
 moves a few queens to free cells, the single-queen descent runs again, and the new minimum is kept when it is no worse; a whole run of
 hops is one launch.  queens_of_boards carries board placements into the cube.  Opt-in like everything here.
+
+tabu_queens, tabu_queens_device and tabu_queens_host walk on from a full_3d placement (include/mcq.h: mcq_tabu3d; csrc/mcq_tabu3d.hip):
+the best admissible move of a conflicting queen to a free cell in every iteration, also when it raises the energy, with the cell left
+forbidden for a while.  A whole run is one launch.  Opt-in like everything here.
 """
 import numpy as np
 
@@ -668,6 +672,145 @@ def hop_queens(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, h
     out = to_numpy(res)
     out["state"], out["best_state"] = out["state"].reshape(s.shape), out["best_state"].reshape(s.shape)
     return out
+
+
+FIELDS_TABU3D = FIELDS_TABU + ("flags",)
+
+
+def _block_tabu3d(N, Q, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter):
+    q = abi.Tabu3d()
+    q.N, q.n_queens, q.n_chains, q.n_iters, q.first_iter = int(N), int(Q), int(n), int(n_iters), int(first_iter)
+    q.tenure, q.tenure_rand, q.tenure_conf = int(tenure), int(tenure_rand), int(tenure_conf)
+    return q
+
+
+def tabu_queens_host(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None,
+                     hist=False, tabu_out=False):
+    """mcq_tabu3d_host: tabu search of full_3d placements in the library's plain host code, NumPy in and out, no GPU.  Same result as
+    tabu_queens, and it runs every shape (the kernel stops where a chain no longer fits the LDS: abi.tabu3d_lds_bytes)."""
+    s = _host_queens(N, states, Q)
+    n = s.shape[0]
+    sd = _hop_seeds(seeds, n)
+    q = _block_tabu3d(N, _queens_of(N, Q), n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
+    width, cube = max(int(n_iters), 0) + 1, max(int(N), 0) ** 3
+    out = _host_outputs(q, s, abi.TABU3D_DTYPES, {"energy_hist": (n, width), "tabu_out": (n, cube)}, _tabu_skip(hist, tabu_out), like=("best_state",))
+    q.seeds, q.hist_stride = sd.ctypes.data, width
+    keep = []
+    if tabu_in is not None:
+        keep.append(np.ascontiguousarray(tabu_in, dtype=np.uint16).reshape(-1))
+        if keep[-1].shape[0] != n * cube:
+            raise ValueError(f"tabu_in must be uint16[n_chains = {n}][N^3 = {cube}], got {np.shape(tabu_in)}")
+        q.tabu_in = keep[-1].ctypes.data
+    if best_floor is not None:
+        keep.append(np.ascontiguousarray(best_floor, dtype=np.int32).reshape(-1))
+        if keep[-1].shape[0] != n:
+            raise ValueError(f"best_floor must be int32[n_chains = {n}], got {np.shape(best_floor)}")
+        q.best_floor = keep[-1].ctypes.data
+    _lib.tabu3d_host(q)
+    return out
+
+
+def tabu_queens_device(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None,
+                       hist=False, tabu_out=False, out=None, stream=None):
+    """mcq_tabu3d_device on a torch uint8 tensor [n_chains][3 Q] or [n_chains][Q][3] of the current device (e.g. DeviceRun.t["best_state"]
+    of a full_3d run; Q=None means N^2) and an int32 or uint32 tensor `seeds` [n_chains] on the same device, enqueued on `stream`
+    (default: torch's current stream).  ONE kernel whatever n_iters is.  Asynchronous: nothing is copied back and nothing synchronises.
+    `tabu_in` (optional) is an int16 or uint16 tensor [n_chains][N^3] (the 16 bits, whatever the sign) and `best_floor` an int32 tensor
+    [n_chains], both of an earlier call.  `out` (optional) is the tensor the final placements go to; it may be `states` itself (in
+    place), default a new one.  Returns a dict of tensors with the fields of FIELDS_TABU3D: `state` and `best_state` uint8 like
+    `states`; `energy_in`, `energy_out`, `best_energy`, `flags` int32[n_chains]; `best_iter`, `n_moves`, `n_aspired`, `n_uphill`,
+    `n_stalled` int64[n_chains]; with hist=True `energy_hist` int32[n_chains][n_iters + 1]; with tabu_out=True `tabu_out`
+    int16[n_chains][N^3] (the uint16 stamps; tabu_to_numpy views them so)."""
+    import torch
+
+    n, Qn = _device_queens("tabu_queens_device", N, states, Q)
+    dev = states.device
+    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
+            and tuple(seeds.shape) == (n,)):
+        raise ValueError(f"tabu_queens_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
+    cube = max(int(N), 0) ** 3
+    if tabu_in is not None and not (isinstance(tabu_in, torch.Tensor) and tabu_in.device == dev and tabu_in.is_contiguous() and tabu_in.numel() == n * cube
+                                    and tabu_in.dtype in (torch.int16, getattr(torch, "uint16", torch.int16))):
+        raise ValueError(f"tabu_queens_device takes tabu_in as a contiguous int16 or uint16 tensor [n_chains = {n}][N^3 = {cube}] on the device of states")
+    if best_floor is not None and not (isinstance(best_floor, torch.Tensor) and best_floor.device == dev and best_floor.is_contiguous()
+                                       and best_floor.dtype == torch.int32 and tuple(best_floor.shape) == (n,)):
+        raise ValueError(f"tabu_queens_device takes best_floor as a contiguous int32 tensor [n_chains = {n}] on the device of states")
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = _block_tabu3d(N, Qn, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
+        width = max(int(n_iters), 0) + 1
+        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
+        for k, dt in abi.TABU3D_DTYPES.items():
+            if k == "energy_hist":
+                if hist:
+                    res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
+            elif k == "tabu_out":
+                if tabu_out:
+                    res[k] = torch.empty((n, cube), dtype=torch.int16, device=dev)
+            else:
+                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
+        if tabu_in is not None:
+            q.tabu_in = tabu_in.data_ptr()
+        if best_floor is not None:
+            q.best_floor = best_floor.data_ptr()
+        for k in abi.TABU3D_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.tabu3d_device(q, st)
+    return res
+
+
+def tabu_queens(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None,
+                hist=False, tabu_out=False):
+    """Tabu search of full_3d placements on the GPU: `states` is uint8[n_chains][3 Q] or [n_chains][Q][3] (Q triples (i, j, k); Q=None
+    means N^2), bytes >= N are clamped to N - 1; `seeds` is uint32[n_chains].  No descent runs first.  Each of the n_iters iterations
+    takes, over the queens that are attacked and the free cells of the cube, the move with the smallest energy change -- a rise too;
+    ties by a random rotation of the queens and of the cells -- whose cell is not tabu, or that leads below the best energy of the run,
+    and the cell it left is tabu for `tenure` iterations + a uniform draw from 0 .. tenure_rand + tenure_conf / 16 per conflicting queen
+    (at most abi.MAX_TABU3D_SPAN in all).  Returns a dict of NumPy arrays with the fields of FIELDS_TABU3D (`energy_hist` only with
+    hist=True, `tabu_out` only with tabu_out=True); best_state is the best placement the call saw, the input when best_iter = 0; flags
+    bit 0 (abi.TABU3D_REPEATED) marks an input with two queens in one cell, which is recounted and handed back unmoved.  A run may be
+    cut as tabu_states says.  A shape whose chain is above the LDS of a workgroup (abi.tabu3d_lds_bytes(N, Q) > abi.MAX_TABU3D_LDS:
+    N = 32 runs up to Q = 14 272 on the device) is run by tabu_queens_host, which gives the same result.  ValueError for what the
+    library refuses (N outside 2 .. 32, Q outside 2 .. N^3 - 1, no chain, tenure outside 0 .. 8192, tenure_rand outside 0 .. 4095,
+    tenure_conf outside 0 .. 64, a negative n_iters or first_iter)."""
+    import torch
+
+    s = _host_queens(N, states, Q)
+    sd = _hop_seeds(seeds, s.shape[0])
+    kw = dict(Q=Q, tenure=tenure, tenure_rand=tenure_rand, tenure_conf=tenure_conf, first_iter=first_iter, hist=hist, tabu_out=tabu_out)
+    if s.shape[0] == 0:
+        _lib.tabu3d_host(_block_tabu3d(N, _queens_of(N, Q), 0, n_iters, tenure, tenure_rand, tenure_conf, first_iter))  # raises the library's refusal
+    if abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and abi.tabu3d_lds_bytes(N, Q) > abi.MAX_TABU3D_LDS:
+        return tabu_queens_host(N, s, sd, n_iters, tabu_in=tabu_in, best_floor=best_floor, **kw)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ti = None if tabu_in is None else torch.from_numpy(np.ascontiguousarray(tabu_in, dtype=np.uint16).view(np.int16)).to(dev)
+    bf = None if best_floor is None else torch.from_numpy(np.ascontiguousarray(best_floor, dtype=np.int32)).to(dev)
+    res = tabu_queens_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_iters, tabu_in=ti, best_floor=bf, **kw)
+    torch.cuda.current_stream(dev).synchronize()
+    out = tabu_to_numpy(res)
+    out["state"], out["best_state"] = out["state"].reshape(s.shape), out["best_state"].reshape(s.shape)
+    return out
+
+
+def check_tabu_queens(tabu_iters, tabu_tenure, tabu_tenure_rand, hops, N, Q, board):
+    """ValueError for what the full_3d annealing hook's `tabu_iters` does not take, before anything is launched."""
+    if int(tabu_iters) < 0:
+        raise ValueError(f"tabu_iters must be >= 0, got {tabu_iters}")
+    if int(tabu_iters) == 0:
+        return
+    if int(hops):
+        raise ValueError("tabu_iters and hops: one search behind the run, not both")
+    if board:
+        raise ValueError('tabu_iters: this hook runs full_3d placements only (mcmc_type="full_3d"); boards go through quench.tabu_states')
+    if not 0 <= int(tabu_tenure) <= abi.MAX_TABU_TENURE:
+        raise ValueError(f"tabu_tenure out of range [0, {abi.MAX_TABU_TENURE}]: {tabu_tenure}")
+    if not 0 <= int(tabu_tenure_rand) <= abi.MAX_TABU_TENURE_RAND:
+        raise ValueError(f"tabu_tenure_rand out of range [0, {abi.MAX_TABU_TENURE_RAND}]: {tabu_tenure_rand}")
+    if abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and abi.tabu3d_lds_bytes(N, Q) > abi.MAX_TABU3D_LDS:
+        raise ValueError(f"tabu_iters: N = {N} with Q = {_queens_of(N, Q)} takes {abi.tabu3d_lds_bytes(N, Q)} bytes of LDS, above the "
+                         f"{abi.MAX_TABU3D_LDS} of a workgroup")
 
 
 def queens_of_boards(N, boards):
