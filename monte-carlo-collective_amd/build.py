@@ -35,9 +35,9 @@ TABU_SOURCES = [os.path.join(CSRC, "mcq_tabu.hip")]
 TABU3D_SOURCES = [os.path.join(CSRC, "mcq_tabu3d.hip")]
 # what the sources include: the C-ABI; the chain record of the sweep and the resume kernels; the attack field of the full_3d files;
 # what the four files outside the sweep (the quenches and the heat baths) share beyond it; the lane helpers of the board heat-bath column
-# update, which the tempered sweep shares
+# update, which the tempered sweep shares; the board table of the pair-move quench, the board hops and the board tabu search
 HEADERS = [os.path.join(os.path.dirname(HERE), "include", "mcq.h"), os.path.join(CSRC, "mcq_record.h"), os.path.join(CSRC, "mcq_field.h"),
-           os.path.join(CSRC, "mcq_post.h"), os.path.join(CSRC, "mcq_columns.h")]
+           os.path.join(CSRC, "mcq_post.h"), os.path.join(CSRC, "mcq_columns.h"), os.path.join(CSRC, "mcq_table.h")]
 HEADER = HEADERS[0]
 # -ffp-contract=off: the reference's schedule / acceptance expressions are evaluated without
 # fused multiply-adds (hipcc's default would contract beta_start + frac * delta into an FMA).

@@ -1,6 +1,7 @@
 // mcq_post.h -- what the kernels that sit outside the sweep share beyond the attack field (csrc/mcq_field.h): csrc/mcq_quench.hip,
-// mcq_heatbath.hip, mcq_quench3d.hip and mcq_heatbath3d.hip.  Philox for the two heat baths, the host count a(c, k) of the two board files,
-// the error text behind every mcq_*_last_error, and for the two full_3d files the threads of the host entry points and the refusals.
+// mcq_heatbath.hip, mcq_quench3d.hip and mcq_heatbath3d.hip.  Philox for the two heat baths, the host count a(c, k) of the board files,
+// the stamp base of the two tabu searches, the error text behind every mcq_*_last_error, and for the two full_3d files the threads of the
+// host entry points and the refusals.
 #ifndef MCQ_POST_H
 #define MCQ_POST_H
 
@@ -37,6 +38,15 @@ __host__ __device__ __forceinline__ void philox_block(uint32_t c0, uint32_t c1, 
         k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
     }
     out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
+}
+
+// the stamp base of the two tabu searches (csrc/mcq_tabu.hip, csrc/mcq_tabu3d.hip): uint16 stamps are kept relative to a base that moves
+// by REBASE every REBASE iterations.  rebase2: both uint16 halves of v less REBASE = 2^15, stopping at 0: a half with its top bit set
+// loses that bit, any other half becomes 0
+constexpr int REBASE = 1 << 15;  // (rebase2 is written for 2^15)
+__device__ __forceinline__ uint32_t rebase2(uint32_t v) {
+    const uint32_t keep = ((v & 0x80008000u) >> 15) * 0xFFFFu;
+    return v & 0x7FFF7FFFu & keep;
 }
 
 // the per-chain figures of a heat-bath call, by one lane or by the host: `a` is a kernel's argument struct or a parameter block

@@ -1,10 +1,10 @@
 // mcq_tabu.hip -- tabu search of board placements: every iteration takes the best admissible single-height move of a conflicting column,
 // also when it raises the energy, and forbids the height it left for a while (include/mcq.h: mcq_tabu, where the rule is stated).  The
-// table a(c, k), its rows and `apply` are those of csrc/mcq_hop.hip, restated here so that file stays as it is; what this file adds is
-// the walk over the table with a stamp per (c, k), as one launch.
+// table a(c, k), its rows and `apply` are those of csrc/mcq_hop.hip: the board table of csrc/mcq_table.h; what this file adds is the walk
+// over the table with a stamp per (c, k), as one launch.
 //
-//   kernel  one chain per wavefront, one wavefront per workgroup, as in the hops.  LDS holds the WHOLE table a(c, k) as one byte per
-//           entry in rows of S bytes, the stamps T(c, k) as one uint16 per entry in rows of TS bytes (S and TS multiples of 4 with an
+//   kernel  one chain per wavefront, one wavefront per workgroup, as in the hops.  LDS holds the WHOLE table a(c, k) in the
+//           layout of csrc/mcq_table.h, the stamps T(c, k) as one uint16 per entry in rows of TS bytes (like S a multiple of 4 with an
 //           odd number of dwords: a lane per column reads its table row and its stamp row as dwords without bank conflicts), the
 //           chain's N^2 heights and its best placement (N^2 bytes, written to global memory once, at the end).  The table is built
 //           ONCE per launch; a move goes through `apply`, which touches at most 6 entries in each of the <= 4 (N - 1) aligned columns.
@@ -14,9 +14,7 @@
 //           ITERATION: the Philox block is computed from values that are uniform over the wavefront.  Each lane takes its columns 64
 //           apart and forms one 32-bit key (delta + 124) << 15 | rho over its admissible candidates (|delta| <= 4 (N - 1) = 124,
 //           rho < N^3 <= 2^15); a __shfl_xor butterfly picks the smallest.  F is a popcount of ballots.  Then one stamp store, `apply`,
-//           E and the counters.  Every data-dependent loop is uniform over the wavefront (one chain), so __syncthreads() is legal
-//           wherever lanes hand LDS data to each other; in a workgroup of one wavefront it is no hardware barrier, only the wait for
-//           the LDS counter and a fence for the compiler.
+//           E and the counters.  The barriers are those of a one-wavefront workgroup (csrc/mcq_table.h).
 //   host    mcq_tabu_host: the same rule over host buffers with plain loops, 64-bit absolute stamps and a table of ints that follows
 //           every move; threaded over chains.
 //
@@ -28,12 +26,14 @@
 
 #include "../../include/mcq.h"
 #include "mcq_post.h"
+#include "mcq_table.h"
 
 namespace {
 
 using mcq_post::fail;
-using mcq_post::host_counts;
 using mcq_post::philox_block;
+using mcq_post::rebase2;
+using mcq_post::REBASE;
 
 thread_local char g_tabu_err[256] = "";
 
@@ -41,7 +41,6 @@ constexpr uint32_t TABU_KEY_WORD = 7u;  // key word 1 of the chain's Philox stre
 constexpr int DELTA_BIAS = 124;         // 4 (MCQ_MAX_N_QUENCH_PAIRS - 1): delta + DELTA_BIAS >= 0
 constexpr int RHO_BITS = 15;            // rho < 32^3
 constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;
-constexpr int REBASE = 1 << 15;         // iterations between two moves of the stamp base (rebase2 below is written for 2^15)
 
 struct TabuArgs {
     const uint32_t* seeds;
@@ -92,28 +91,6 @@ __host__ __device__ __forceinline__ void tabu_draw(uint32_t seed, unsigned long 
     jitter = (int)(((unsigned long long)r[1] * (unsigned)(tenure_rand + 1)) >> 32);
 }
 
-__host__ __device__ __forceinline__ int att(int k, int kk, int d) {
-    const int x = k > kk ? k - kk : kk - k;
-    return (x == 0) | (x == d);
-}
-
-// slot t = 0 .. 4 N - 1 of column (i, j): position p = t mod N of its row, its board column, its diagonal, its antidiagonal.  True when
-// the slot names another column of the board, c2, at distance d; every aligned column has exactly one slot.
-__device__ __forceinline__ bool aligned_slot(int N, int i, int j, int t, int& c2, int& d) {
-    const int f = (t >= N) + (t >= 2 * N) + (t >= 3 * N), p = t - f * N;
-    const int off = p - (f == 1 ? i : j);
-    d = off < 0 ? -off : off;
-    const int r = f == 0 ? i : f == 1 ? p : f == 2 ? i + off : i - off;
-    c2 = r * N + (f == 1 ? j : p);
-    return t < 4 * N && off != 0 && r >= 0 && r < N;
-}
-
-// both uint16 halves of v less REBASE = 2^15, stopping at 0: a half with its top bit set loses that bit, any other half becomes 0
-__device__ __forceinline__ uint32_t rebase2(uint32_t v) {
-    const uint32_t keep = ((v & 0x80008000u) >> 15) * 0xFFFFu;
-    return v & 0x7FFF7FFFu & keep;
-}
-
 template <int NP>
 constexpr int tabu_lds_bytes() {
     return NP * NP * (4 * ((NP / 4) | 1) + 4 * ((NP / 2) | 1) + 2);
@@ -121,15 +98,14 @@ constexpr int tabu_lds_bytes() {
 
 template <int NP>
 __global__ __launch_bounds__(64) void mcq_tabu_kernel(TabuArgs a) {
-    constexpr int QP = NP * NP;
-    constexpr int SW = (NP / 4) | 1, S = 4 * SW;    // dwords and bytes of a table row
-    constexpr int RW = NP / 4;                      // dwords of a table row that hold entries
+    using R = mcq_table::Rows<NP>;
+    constexpr int QP = R::QP, SW = R::SW, S = R::S, RW = R::RW;
     constexpr int TW = (NP / 2) | 1, TS = 2 * TW;   // dwords and uint16s of a stamp row
     __shared__ uint32_t tab32[QP * SW];
     __shared__ uint32_t stamp32[QP * TW];
     __shared__ uint8_t h[QP], best[QP];
     static_assert(sizeof(tab32) + sizeof(stamp32) + sizeof(h) + sizeof(best) == tabu_lds_bytes<NP>(), "the LDS of a chain, as the host checks it");
-    uint8_t* tab = reinterpret_cast<uint8_t*>(tab32);
+    const uint8_t* tab = reinterpret_cast<const uint8_t*>(tab32);
     uint16_t* stamp = reinterpret_cast<uint16_t*>(stamp32);
     const int N = a.N, Q = N * N, N3 = Q * N;
     const int lane = threadIdx.x;
@@ -137,11 +113,10 @@ __global__ __launch_bounds__(64) void mcq_tabu_kernel(TabuArgs a) {
     const uint32_t seed = a.seeds[ch];
     const uint8_t* in = a.state_in + ch * Q;
     for (int c = lane; c < Q; c += 64) {
-        const int v = in[c];
-        const uint8_t hc = (uint8_t)(v < N ? v : N - 1);
+        const uint8_t hc = mcq_table::clamped(in[c], N);
         h[c] = hc, best[c] = hc;
     }
-    for (int w = lane; w < Q * SW; w += 64) tab32[w] = 0xFFFFFFFFu;
+    mcq_table::fill<NP>(tab32, Q, lane);
     for (int w = lane; w < Q * TW; w += 64) stamp32[w] = 0u;
     __syncthreads();
     if (a.tabu_in) {
@@ -151,49 +126,12 @@ __global__ __launch_bounds__(64) void mcq_tabu_kernel(TabuArgs a) {
             stamp[c * TS + k] = ti[e];
         }
     }
-    for (int e = lane; e < N3; e += 64) {  // the table, one lane per entry
-        const int c = e / N, k = e - c * N, i = c / N, j = c - i * N;
-        int cnt = 0;
-        auto hit = [&](int hp, int d) { cnt += att(hp, k, d); };
-        for (int jj = 0; jj < N; jj++) {  // the row, and the two diagonal cells of board column jj
-            if (jj == j) continue;
-            const int d = jj > j ? jj - j : j - jj;
-            hit(h[i * N + jj], d);
-            if (i + d < N) hit(h[(i + d) * N + jj], d);
-            if (i - d >= 0) hit(h[(i - d) * N + jj], d);
-        }
-        for (int ii = 0; ii < N; ii++)  // the board column
-            if (ii != i) hit(h[ii * N + j], ii > i ? ii - i : i - ii);
-        tab[c * S + k] = (uint8_t)cnt;
-    }
-    __syncthreads();
-
-    int twoE = 0;
-    for (int c = lane; c < Q; c += 64) twoE += tab[c * S + h[c]];
-    for (int o = 32; o; o >>= 1) twoE += __shfl_xor(twoE, o);
-    const int e_in = twoE >> 1;
+    mcq_table::build<NP>(tab32, h, N, lane);
+    const int e_in = mcq_table::energy<NP>(tab32, h, N, lane);
     int E = e_in, B = e_in;
     if (a.best_floor) B = min(B, a.best_floor[ch]);
     long long moves = 0, aspired = 0, uphill = 0, stalled = 0, best_iter = 0;
     if (a.energy_hist && lane == 0) a.energy_hist[ch * a.hist_stride] = E;
-
-    // column c takes the height hn: the table rows of its aligned columns follow, one lane per aligned column
-    auto apply = [&](int c, int hn) {
-        const int i = c / N, j = c - i * N, ho = h[c];
-        for (int t = lane; t < 4 * N; t += 64) {
-            int c2, d;
-            if (!aligned_slot(N, i, j, t, c2, d)) continue;
-            uint8_t* row = tab + c2 * S;
-            row[ho]--;
-            if (ho - d >= 0) row[ho - d]--;
-            if (ho + d < N) row[ho + d]--;
-            row[hn]++;
-            if (hn - d >= 0) row[hn - d]++;
-            if (hn + d < N) row[hn + d]++;
-        }
-        h[c] = (uint8_t)hn;
-        __syncthreads();
-    };
 
     long long t_base = 0;  // the iteration of the call at which the stamps' base lies
     for (long long t = 0; t < a.n_iters; t++) {
@@ -251,7 +189,7 @@ __global__ __launch_bounds__(64) void mcq_tabu_kernel(TabuArgs a) {
             uphill += delta > 0;
             moves++;
             if (lane == 0) stamp[c * TS + ho] = (uint16_t)(now_rel + 1 + L);
-            apply(c, k);
+            mcq_table::apply<NP>(tab32, h, N, lane, c, k);
             E += delta;
             if (E < B) {
                 B = E, best_iter = t + 1;
@@ -280,8 +218,7 @@ __global__ __launch_bounds__(64) void mcq_tabu_kernel(TabuArgs a) {
 }
 
 int lds_bytes(int N) {
-    return N <= 4 ? tabu_lds_bytes<4>() : N <= 8 ? tabu_lds_bytes<8>() : N <= 12 ? tabu_lds_bytes<12>() : N <= 16 ? tabu_lds_bytes<16>()
-         : N <= 24 ? tabu_lds_bytes<24>() : tabu_lds_bytes<32>();
+    return mcq_table::for_rows_of(N, [](auto rows) { return tabu_lds_bytes<decltype(rows)::NP>(); });
 }
 
 // what both entry points refuse
@@ -320,17 +257,11 @@ void host_chain(const mcq_tabu* q, long long ch) {
     std::vector<uint8_t> h((size_t)Q), best((size_t)Q);
     std::vector<int> A((size_t)N3);
     std::vector<long long> T((size_t)N3, 0LL);
-    const uint8_t* in = q->state_in + ch * Q;
-    for (int c = 0; c < Q; c++) h[(size_t)c] = (uint8_t)(in[c] < N ? in[c] : N - 1);
+    mcq_table::host_load(q->state_in + ch * Q, N, h.data());
     best = h;
     if (q->tabu_in)
         for (int e = 0; e < N3; e++) T[(size_t)e] = q->first_iter + (long long)q->tabu_in[ch * N3 + e];
-    long long twoE = 0;
-    for (int c = 0; c < Q; c++) {
-        host_counts(h.data(), N, c / N, c % N, A.data() + (size_t)c * N);
-        twoE += A[(size_t)c * N + h[(size_t)c]];
-    }
-    const int e_in = (int)(twoE / 2);
+    const int e_in = mcq_table::host_table(h.data(), N, A.data());
     int E = e_in, B = e_in;
     if (q->best_floor && q->best_floor[ch] < B) B = q->best_floor[ch];
     long long moves = 0, aspired = 0, uphill = 0, stalled = 0, best_iter = 0;
@@ -413,13 +344,9 @@ int mcq_tabu_device(const mcq_tabu* q, void* hip_stream) {
                      q->best_iter, q->best_state, q->n_moves, q->n_aspired, q->n_uphill, q->n_stalled, q->energy_hist, (long long)q->hist_stride,
                      (long long)q->n_chains, (long long)q->n_iters, (long long)q->first_iter, (int)q->tenure, (int)q->tenure_rand,
                      (int)q->tenure_conf, (int)q->N};
-    const dim3 grid((unsigned)a.n_chains), block(64);
-    if (q->N <= 4) hipLaunchKernelGGL(mcq_tabu_kernel<4>, grid, block, 0, s, a);
-    else if (q->N <= 8) hipLaunchKernelGGL(mcq_tabu_kernel<8>, grid, block, 0, s, a);
-    else if (q->N <= 12) hipLaunchKernelGGL(mcq_tabu_kernel<12>, grid, block, 0, s, a);
-    else if (q->N <= 16) hipLaunchKernelGGL(mcq_tabu_kernel<16>, grid, block, 0, s, a);
-    else if (q->N <= 24) hipLaunchKernelGGL(mcq_tabu_kernel<24>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(mcq_tabu_kernel<32>, grid, block, 0, s, a);
+    mcq_table::for_rows_of(q->N, [&](auto rows) {
+        hipLaunchKernelGGL(mcq_tabu_kernel<decltype(rows)::NP>, dim3((unsigned)a.n_chains), dim3(64), 0, s, a);
+    });
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(g_tabu_err, MCQ_EDEVICE, "mcq_tabu_device: %s", hipGetErrorString(e));
     return MCQ_OK;

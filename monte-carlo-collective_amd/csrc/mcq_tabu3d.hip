@@ -1,7 +1,7 @@
 // mcq_tabu3d.hip -- tabu search of full_3d placements: every iteration takes the best admissible move of a conflicting queen to a free
 // cell of the cube, also when it raises the energy, and forbids the cell it left for a while (include/mcq.h: mcq_tabu3d, where the rule
 // is stated).  The field, its update and the start of a chain are those of csrc/mcq_field.h; the stamp base is that of csrc/mcq_tabu.hip,
-// restated here so that file stays as it is.
+// which both files take from csrc/mcq_post.h.
 //
 //   kernel  one chain per workgroup of W lanes, all in LDS: red, 32 dwords; the stamps T(t), one uint16 per cell, relative to a base
 //           that moves by 2^15 every 2^15 iterations; then the field S of the WHOLE placement, occ and the queens (csrc/mcq_field.h).
@@ -36,6 +36,8 @@ using namespace mcq_field;
 using mcq_post::fail;
 using mcq_post::philox_block;
 using mcq_post::queens_of;
+using mcq_post::rebase2;
+using mcq_post::REBASE;
 
 thread_local char g_tabu3d_err[256] = "";
 
@@ -45,7 +47,6 @@ constexpr int DELTA_BIAS = 13 * (MCQ_MAX_N_QUENCH3D - 1);  // 403: |delta| <= 13
 constexpr uint32_t RHO_MASK = (1u << RHO_BITS) - 1u;
 constexpr uint32_t KEY_NONE = 0xFFFFFFFFu;                 // a cell key S << 15 | rho_t stays below 2^24 (S <= 13 (N - 1) + 1 = 404 < 2^9)
 constexpr unsigned long long KEY64_NONE = ~0ull;           // a move key stays below 2^40
-constexpr int REBASE = 1 << 15;           // iterations between two moves of the stamp base (rebase2 below is written for 2^15)
 static_assert(MCQ_MAX_TABU3D_SPAN + REBASE + 1 < (1 << 16), "a stamp written just before the base moves fits 16 bits");
 
 struct Tabu3dArgs {
@@ -110,12 +111,6 @@ __host__ __device__ __forceinline__ int tabu3d_span(int tenure, int jitter, int 
 __host__ __device__ __forceinline__ void clip_steps(int dc, int x, int N, int& lo, int& hi) {
     if (dc > 0) lo = lo > -x ? lo : -x, hi = hi < N - 1 - x ? hi : N - 1 - x;
     if (dc < 0) lo = lo > x - (N - 1) ? lo : x - (N - 1), hi = hi < x ? hi : x;
-}
-
-// both uint16 halves of v less REBASE = 2^15, stopping at 0: a half with its top bit set loses that bit, any other half becomes 0
-__device__ __forceinline__ uint32_t rebase2(uint32_t v) {
-    const uint32_t keep = ((v & 0x80008000u) >> 15) * 0xFFFFu;
-    return v & 0x7FFF7FFFu & keep;
 }
 
 // the minima of x and of y over the workgroup, through red[0 .. 15] and red[16 .. 31]
