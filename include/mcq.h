@@ -1292,6 +1292,85 @@ int mcq_tabu3d_device(const mcq_tabu3d* q, void* hip_stream);
  * to the kernel bit for bit on every output. */
 int mcq_tabu3d_host(const mcq_tabu3d* q);
 
+/*
+ * Path relinking between board placements: walk from a placement A towards a guide G, one column at a time, always the cheapest
+ * remaining column, and hand the best placement met on the way to the local search (csrc/mcq_relink.hip) -- NOT a mode of the
+ * reference; never a default, like everything above that is labelled so.  Every search above moves one placement; this block
+ * combines two.  Boards only.  The rule is integer-exact:
+ *   1. SETUP.  Every byte of state_in and of guide_in is clamped to N - 1 first; a(c, k), E and delta(c, k) = a(c, k) - a(c, h(c))
+ *      are those of the mcq_tabu rule, item 1.  h is the walking placement and starts as the clamped A = state_in; g is the clamped
+ *      guide.  F = {c : h(c) != g(c)} and d0 = |F| at the start (distance_in).  energy_in is the recount of A.
+ *   2. WALK.  n_steps = d0 when max_steps = 0, else min(d0, max_steps).  Step t = 0 .. n_steps - 1 draws one block
+ *        (x0, x1, x2, x3) = philox4x32-10(counter = (t, low 32 bits of walk, high 32 bits of walk, 0), key = (seeds[r], 9))
+ *      (key words 0 - 8 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d, mcq_tabu and
+ *      mcq_tabu3d; 9 is this block's).  o = floor(x0 N^2 / 2^32); x1, x2 and x3 are unused.  Of the columns c in F the step takes
+ *      the one with the lexicographically smallest (delta(c, g(c)), (c - o) mod N^2); then h(c) = g(c), E += delta and c leaves F.
+ *      A rise is taken like a fall.  walk >= 0 is a caller's index, so that repeated walks from the same seeds take different tie
+ *      orders.
+ *   3. CANDIDATES.  The placement behind step t (t counted from 1 here) is at distance t from A and d0 - t from G.  It is a CANDIDATE
+ *      when t >= max(1, min_dist) and d0 - t >= min_dist.  P* is the candidate with the smallest E, the earliest on ties:
+ *      path_best_step = its t, path_best_energy = its E.  With no candidate P* is the clamped A, path_best_step = 0 and
+ *      path_best_energy = energy_in.  P* need not lie below A.  path_best_state = P*.  path_max_energy is the largest entry of the
+ *      walk's energies, energy_in included.
+ *   4. LOCAL SEARCH.  L of the mcq_hop rule, item 2, by local_search (MCQ_HOP_SINGLE or MCQ_HOP_PAIRS), runs on P*: state_out and
+ *      energy_out are the placement and E behind it, n_moves and n_pair_moves its single and pair moves (int64).
+ *   5. HISTORY.  energy_hist[r][0 .. W], W = max_steps, or N^2 when that is 0: entry 0 is energy_in, entry t is E behind step t, and
+ *      the entries behind n_steps repeat the last one.  hist_stride >= W + 1 when energy_hist is given.
+ * Consequences:
+ *   (a) with d0 = 0 the call is L alone: state_out, energy_out, n_moves and n_pair_moves are those of mcq_quench_pairs with
+ *       max_rounds = 0 (MCQ_HOP_PAIRS) or of mcq_quench with max_passes = 0 (MCQ_HOP_SINGLE).
+ *   (b) with max_steps = 0 the walk ends on g: entry d0 of the history is the energy_in of a call whose state_in is the guide.
+ *   (c) state_out is a fixed point of L.
+ *   (d) path_best_energy = E of path_best_state, and energy_out <= path_best_energy.
+ * N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS on the device and in host code alike.  Chains do not interact and a call reads all of a
+ * chain's inputs before it writes any of its outputs, so state_out may be state_in; it may not be guide_in (the guides stay the
+ * caller's: a pool that relinks each slot with a rolled view of itself reads them again).  path_best_state is none of state_in,
+ * guide_in and state_out.
+ *
+ * mcq_relink_device keeps a chain in the LDS of one wavefront: the table a(c, k) as bytes in rows of 4 ((NP / 4) | 1) bytes, the
+ * heights h, g and P* (a byte per column each) and, under MCQ_HOP_PAIRS, the two mask words per column of the pair scan, NP = N
+ * rounded up to 4, 8, 12, 16, 24 or 32:
+ *   bytes = NP^2 (4 ((NP / 4) | 1) + 3), and 8 NP^2 more under MCQ_HOP_PAIRS:  48 128 at NP = 32, <= MCQ_MAX_RELINK_LDS.
+ */
+#define MCQ_MAX_RELINK_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_relink_device may take */
+typedef struct mcq_relink {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS */
+    int32_t mode;           /* MCQ_MODE_BOARD; anything else is MCQ_EINVAL */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int32_t max_steps;      /* 0 .. N^2; 0 = the whole way to the guide */
+    int32_t min_dist;       /* 0 .. N^2: a candidate is at least this far from the guide, and max(1, min_dist) from A */
+    int32_t local_search;   /* MCQ_HOP_SINGLE or MCQ_HOP_PAIRS */
+    int64_t walk;           /* >= 0: the caller's index of the walk, counter words 1 and 2 of the tie offsets' blocks */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout: A */
+    const uint8_t* guide_in; /* [n_chains][N*N]: G */
+    uint8_t* state_out;     /* [n_chains][N*N]; may be state_in, may not be guide_in */
+    uint8_t* path_best_state; /* optional [n_chains][N*N]: P*; none of state_in, guide_in, state_out */
+    int32_t* distance_in;   /* optional [n_chains]: d0 */
+    int32_t* n_steps;       /* optional [n_chains] */
+    int32_t* path_best_step; /* optional [n_chains]: 0 = no candidate (P* = A), else t of P* */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) A, recounted */
+    int32_t* path_best_energy; /* optional [n_chains]: E of P* */
+    int32_t* path_max_energy; /* optional [n_chains]: the largest energy of the walk, energy_in included */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int64_t* n_moves;       /* optional [n_chains]: single moves of L */
+    int64_t* n_pair_moves;  /* optional [n_chains]: pair moves of L (0 under MCQ_HOP_SINGLE) */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. W, W = max_steps or N^2 */
+    int64_t hist_stride;    /* >= W + 1 when energy_hist is given; not read otherwise */
+} mcq_relink;
+
+/* the message of the last error of the calling thread from the two mcq_relink_* calls below (they do not set mcq_last_error()) */
+const char* mcq_relink_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever the distances are; asynchronous: nothing
+ * is copied back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, mode other
+ * than board, N out of range, n_chains outside 1 .. 2^31 - 1, max_steps or min_dist outside 0 .. N^2, a local_search that is neither
+ * value, a negative walk, a NULL seeds, state_in, guide_in or state_out, a state_out that is guide_in, a path_best_state that is
+ * state_in, guide_in or state_out, hist_stride below W + 1 when energy_hist is given, and a chain above MCQ_MAX_RELINK_LDS (no N in
+ * range is). */
+int mcq_relink_device(const mcq_relink* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
+int mcq_relink_host(const mcq_relink* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -239,6 +239,11 @@ def lib():
         L.mcq_tabu3d_device.argtypes = [C.POINTER(abi.Tabu3d), C.c_void_p]
         L.mcq_tabu3d_host.restype = C.c_int
         L.mcq_tabu3d_host.argtypes = [C.POINTER(abi.Tabu3d)]
+        L.mcq_relink_last_error.restype = C.c_char_p
+        L.mcq_relink_device.restype = C.c_int
+        L.mcq_relink_device.argtypes = [C.POINTER(abi.Relink), C.c_void_p]
+        L.mcq_relink_host.restype = C.c_int
+        L.mcq_relink_host.argtypes = [C.POINTER(abi.Relink)]
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
@@ -426,6 +431,28 @@ def tabu3d_host(q):
 def tabu3d_device(q, stream):
     """mcq_tabu3d_device on a filled abi.Tabu3d block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
     _check_tabu3d(lib().mcq_tabu3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+
+
+def _check_relink(rc):
+    """_check for the mcq_relink_* calls, which keep their own message (mcq_relink_last_error)."""
+    if rc == abi.OK:
+        return
+    msg = lib().mcq_relink_last_error().decode(errors="replace")
+    if rc == abi.EINVAL:
+        raise ValueError(msg)
+    if rc == abi.ENOMEM:
+        raise MemoryError(msg)
+    raise McqError(msg)
+
+
+def relink_host(q):
+    """mcq_relink_host on a filled abi.Relink block of HOST pointers.  Pure host code, no GPU."""
+    _check_relink(lib().mcq_relink_host(C.byref(q)))
+
+
+def relink_device(q, stream):
+    """mcq_relink_device on a filled abi.Relink block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
+    _check_relink(lib().mcq_relink_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
 
 
 def _check_quench3d(rc):

@@ -405,6 +405,50 @@ def tabu3d_lds_bytes(N, Q=None):
     return 4 * (32 + -(-cells // 2) + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2)
 
 
+MAX_RELINK_LDS = 160 * 1024    # include/mcq.h: MCQ_MAX_RELINK_LDS
+
+
+class Relink(C.Structure):
+    """include/mcq.h: mcq_relink -- path relinking between board placements: walk towards a guide, the best placement on the way to the local search"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("max_steps", C.c_int32),
+        ("min_dist", C.c_int32),
+        ("local_search", C.c_int32),
+        ("walk", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("guide_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("path_best_state", C.c_void_p),
+        ("distance_in", C.c_void_p),
+        ("n_steps", C.c_void_p),
+        ("path_best_step", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("path_best_energy", C.c_void_p),
+        ("path_max_energy", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_pair_moves", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+    ]
+
+
+# the per-chain outputs of a relink call besides the placements (state, path_best_state): field -> dtype ("energy_hist" has a row of
+# W + 1 per chain, W = max_steps or N^2)
+RELINK_DTYPES = {"distance_in": np.int32, "n_steps": np.int32, "path_best_step": np.int32, "energy_in": np.int32, "path_best_energy": np.int32,
+                 "path_max_energy": np.int32, "energy_out": np.int32, "n_moves": np.int64, "n_pair_moves": np.int64, "energy_hist": np.int32}
+
+
+def relink_lds_bytes(N, pairs=True):
+    """The bytes of LDS a chain of mcq_relink_device takes (include/mcq.h, below the rule): table, three placements and the scan's masks."""
+    NP = next(p for p in (4, 8, 12, 16, 24, 32) if int(N) <= p)
+    return NP * NP * (4 * ((NP // 4) | 1) + 3) + (8 * NP * NP if pairs else 0)
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

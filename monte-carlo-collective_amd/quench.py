@@ -20,6 +20,12 @@ csrc/mcq_tabu.hip): tabu search, that is the best admissible single-height move 
 it raises the energy, with the height left forbidden for a while.  A whole run is one launch.  Boards, N = 2 .. 32; opt-in like
 everything here.
 
+relink_states, relink_device and relink_host combine two placements (include/mcq.h: mcq_relink; csrc/mcq_relink.hip): path relinking, that
+is a walk from a placement towards a guide, one column at a time and always the cheapest remaining one, with the best placement met on
+the way handed to the single-move or the pair-move descent.  board_images and nearest_image bring a guide into the one of its 16
+symmetric images that is closest to the placement, and relink_pool runs rounds of relinking over a pool of placements, each slot with a
+rolled partner.  A whole call is one launch.  Boards, N = 2 .. 32; opt-in like everything here.
+
 full_3d placements have a rule and a kernel of their own (include/mcq.h: mcq_quench3d; csrc/mcq_quench3d.hip), N = 2 .. 32 and
 2 <= Q <= N^3 - 1: quench_queens, quench_queens_device, quench_queens_host.  The same labels apply -- the reference ships
 conflicts_for_queen (mcmc.py:185-226) and never calls it.
@@ -482,6 +488,252 @@ def check_tabu(tabu_iters, tabu_tenure, hops, N, board=True):
         raise ValueError(f"tabu_iters: N out of range [{abi.MIN_N}, {abi.MAX_N_QUENCH_PAIRS}]: {N}")
     if not 0 <= int(tabu_tenure) <= abi.MAX_TABU_TENURE:
         raise ValueError(f"tabu_tenure out of range [0, {abi.MAX_TABU_TENURE}]: {tabu_tenure}")
+
+
+FIELDS_RELINK = ("state", "path_best_state", "distance_in", "n_steps", "path_best_step", "energy_in", "path_best_energy", "path_max_energy",
+                 "energy_out", "n_moves", "n_pair_moves", "energy_hist")
+
+
+def _block_relink(N, n, max_steps, min_dist, local_search, walk):
+    if local_search not in abi.HOP_LOCAL_SEARCH:
+        raise ValueError(f'local_search must be "single" or "pairs", got {local_search!r}')
+    q = abi.Relink()
+    q.N, q.mode, q.n_chains, q.walk = int(N), abi.MODE_BOARD, int(n), int(walk)
+    q.max_steps, q.min_dist, q.local_search = int(max_steps), int(min_dist), abi.HOP_LOCAL_SEARCH[local_search]
+    return q
+
+
+def _relink_width(N, max_steps):
+    """W + 1 of the rule, item 5: the entries of a chain's history."""
+    return (int(max_steps) if int(max_steps) > 0 else max(int(N), 0) ** 2) + 1
+
+
+def _relink_skip(hist, figures):
+    return tuple(k for k in abi.RELINK_DTYPES if (k == "energy_hist" and not hist) or (k != "energy_hist" and not figures))
+
+
+def relink_host(N, states, guides, seeds, max_steps=0, min_dist=1, local_search="pairs", walk=0, hist=False, figures=True):
+    """mcq_relink_host: path relinking in the library's plain host code, NumPy in and out, no GPU.  Same result as relink_states."""
+    s, g = _host_states(N, states), _host_states(N, guides)
+    n = s.shape[0]
+    if g.shape != s.shape:
+        raise ValueError(f"guides must have the shape of states, {s.shape}, got {g.shape}")
+    sd = _hop_seeds(seeds, n)
+    q = _block_relink(N, n, max_steps, min_dist, local_search, walk)
+    width = _relink_width(N, max_steps)
+    out = _host_outputs(q, s, abi.RELINK_DTYPES, {"energy_hist": (n, width)}, _relink_skip(hist, figures), like=("path_best_state",) if figures else ())
+    q.seeds, q.guide_in, q.hist_stride = sd.ctypes.data, g.ctypes.data, width
+    _lib.relink_host(q)
+    return out
+
+
+def relink_device(N, states, guides, seeds, max_steps=0, min_dist=1, local_search="pairs", walk=0, hist=False, figures=True, out=None, stream=None):
+    """mcq_relink_device on two torch uint8 tensors [n_chains][N*N] of the current device, the placements and their guides, and an int32
+    or uint32 tensor `seeds` [n_chains] on the same device, enqueued on `stream` (default: torch's current stream).  ONE kernel whatever
+    the distances are.  Asynchronous: nothing is copied back and nothing synchronises.  `out` (optional) is the tensor the final
+    placements go to; it may be `states` itself (in place) and may not be `guides`; default a new one.  Returns a dict of tensors with
+    the fields of FIELDS_RELINK: `state` and `path_best_state` uint8 like `states`; `distance_in`, `n_steps`, `path_best_step`,
+    `energy_in`, `path_best_energy`, `path_max_energy`, `energy_out` int32[n_chains]; `n_moves`, `n_pair_moves` int64[n_chains]; with
+    hist=True `energy_hist` int32[n_chains][W + 1], W = max_steps or N^2.  figures=False leaves every optional output but the history
+    out: `state` alone."""
+    import torch
+
+    n = _device_states("relink_device", N, states)
+    dev = states.device
+    if not (isinstance(guides, torch.Tensor) and guides.device == dev and guides.dtype == torch.uint8 and guides.is_contiguous() and guides.shape == states.shape):
+        raise ValueError("relink_device takes guides as a contiguous uint8 tensor of the shape and device of states")
+    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
+            and tuple(seeds.shape) == (n,)):
+        raise ValueError(f"relink_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = _block_relink(N, n, max_steps, min_dist, local_search, walk)
+        width = _relink_width(N, max_steps)
+        res = {"state": _device_out(out, states)}
+        if figures:
+            res["path_best_state"] = torch.empty_like(states)
+            q.path_best_state = res["path_best_state"].data_ptr()
+        for k, dt in abi.RELINK_DTYPES.items():
+            if k == "energy_hist":
+                if hist:
+                    res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
+            elif figures:
+                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
+        q.seeds, q.state_in, q.guide_in, q.state_out, q.hist_stride = seeds.data_ptr(), states.data_ptr(), guides.data_ptr(), res["state"].data_ptr(), width
+        for k in abi.RELINK_DTYPES:
+            if k in res:
+                setattr(q, k, res[k].data_ptr())
+        _lib.relink_device(q, st)
+    return res
+
+
+def relink_states(N, states, guides, seeds, max_steps=0, min_dist=1, local_search="pairs", walk=0, hist=False, figures=True):
+    """Path relinking of board placements on the GPU: `states` and `guides` are uint8[n_chains][N*N] (one board of N*N heights is taken
+    as one chain), bytes >= N are clamped to N - 1; `seeds` is uint32[n_chains].  Each placement walks towards its guide: a step gives
+    one of the columns in which the two differ the guide's height, the column whose change of energy is smallest -- a rise too; ties by
+    a random rotation that `walk` and the seed decide --, for max_steps steps or, with 0, all the way.  Of the placements on the way that
+    are at least max(1, min_dist) columns from the start and min_dist from the guide, the one with the smallest energy (`path_best_state`,
+    the start when there is none) then descends under the local search -- "single": single-height moves, "pairs": those and moves of
+    two aligned columns -- to `state`.  Returns a dict of NumPy arrays with the fields of FIELDS_RELINK (`energy_hist` only with
+    hist=True: the energies along the walk, whose largest is `path_max_energy`, the barrier when less `energy_in`).  ValueError for what
+    the library refuses (N outside 2 .. 32, no chain, max_steps or min_dist outside 0 .. N^2, a negative walk)."""
+    import torch
+
+    s, g = _host_states(N, states), _host_states(N, guides)
+    if g.shape != s.shape:
+        raise ValueError(f"guides must have the shape of states, {s.shape}, got {g.shape}")
+    sd = _hop_seeds(seeds, s.shape[0])
+    if s.shape[0] == 0:
+        _lib.relink_host(_block_relink(N, 0, max_steps, min_dist, local_search, walk))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = relink_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(g).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), max_steps=max_steps,
+                        min_dist=min_dist, local_search=local_search, walk=walk, hist=hist, figures=figures)
+    torch.cuda.current_stream(dev).synchronize()
+    return to_numpy(res)
+
+
+N_IMAGES = 16  # the symmetries of the square times the flip of the heights
+
+
+def _images(N, b):
+    """board_images without its checks: b is [n][N][N], a NumPy array or a torch tensor; returns the list of the 16 images."""
+    torch_like = not isinstance(b, np.ndarray)
+    out = []
+    for f in (0, 1):
+        x = (N - 1) - b if f else b
+        for m in (0, 1):
+            y = (x.transpose(1, 2) if torch_like else x.swapaxes(1, 2)) if m else x
+            for r in range(4):
+                out.append(y.rot90(r, (1, 2)) if torch_like else np.rot90(y, r, axes=(1, 2)))
+    return out
+
+
+def board_images(N, states):
+    """The 16 symmetric images of board placements as [16][n][N*N]: `states` is uint8[n][N*N], a NumPy array or a torch tensor (the
+    result is of the same kind, on the same device).  Image s = 8 f + 4 m + r of the board B (B[i][j] the height of column (i, j)) is
+    rot90^r(T^m(F^f(B))): first, with f = 1, every height k becomes N - 1 - k; then, with m = 1, the board is transposed; then it
+    is turned r quarter turns counter-clockwise (numpy.rot90).  Image 0 is the board itself.  All 16 have the energy of the board: a
+    symmetry of the square keeps rows, columns, diagonals and distances, and the flip keeps |k - k'|.  ValueError for an entry >= N (a
+    height that the rule would clamp has no flip)."""
+    N = int(N)
+    if not abi.MIN_N <= N <= abi.MAX_N_BOARD:
+        raise ValueError(f"N out of range [{abi.MIN_N}, {abi.MAX_N_BOARD}]: {N}")
+    if isinstance(states, np.ndarray) or not hasattr(states, "is_cuda"):
+        s = _host_states(N, states)
+        if s.size and int(s.max()) >= N:
+            raise ValueError(f"board_images: an entry of states is >= N = {N}")
+        return np.stack(_images(N, s.reshape(-1, N, N))).reshape(N_IMAGES, s.shape[0], N * N)
+    import torch
+
+    if states.dtype != torch.uint8 or states.dim() != 2 or int(states.shape[1]) != N * N:
+        raise ValueError(f"states must be uint8[n][{N * N}] (final_state layout of a board), got {tuple(states.shape)}")
+    if states.numel() and int(states.max()) >= N:
+        raise ValueError(f"board_images: an entry of states is >= N = {N}")
+    return torch.stack(_images(N, states.reshape(-1, N, N))).reshape(N_IMAGES, states.shape[0], N * N)
+
+
+def _nearest(N, s, imgs):
+    """(image, index, distance) of nearest_image from the stacked images [16][n][N*N] of the guides; s is [n][N*N]."""
+    torch_like = not isinstance(s, np.ndarray)
+    if torch_like:
+        import torch
+
+        dist = (imgs != s.unsqueeze(0)).sum(dim=2)  # [16][n]
+        key = (dist * N_IMAGES + torch.arange(N_IMAGES, device=s.device).unsqueeze(1)).min(dim=0).values  # the smallest index of the smallest distance
+        idx = key % N_IMAGES
+        return imgs[idx, torch.arange(s.shape[0], device=s.device)].contiguous(), idx.to(torch.int32), (key // N_IMAGES).to(torch.int32)
+    dist = (imgs != s[None]).sum(axis=2).astype(np.int64)
+    key = (dist * N_IMAGES + np.arange(N_IMAGES)[:, None]).min(axis=0)
+    idx = key % N_IMAGES
+    return np.ascontiguousarray(imgs[idx, np.arange(s.shape[0])]), idx.astype(np.int32), (key // N_IMAGES).astype(np.int32)
+
+
+def nearest_image(N, states, guides):
+    """Of the 16 images of each guide (board_images) the one closest to its state in Hamming distance: returns (the images uint8[n][N*N],
+    their indices int32[n] in board_images' numbering, the distances int32[n]); the smallest index on ties.  Two minima that are mirror
+    images of one another are N^2 columns apart and relink through noise; aligned, the walk is as short as the symmetry allows, and the
+    guide's energy is the same.  NumPy arrays or torch tensors, both of the same kind; ValueError for an entry >= N in either."""
+    imgs = board_images(N, guides)
+    if isinstance(imgs, np.ndarray):
+        s = _host_states(N, states)
+        if s.shape != imgs.shape[1:]:
+            raise ValueError(f"states must have the shape of guides, {imgs.shape[1:]}, got {s.shape}")
+        if s.size and int(s.max()) >= int(N):
+            raise ValueError(f"nearest_image: an entry of states is >= N = {int(N)}")
+        return _nearest(int(N), s, imgs)
+    if not hasattr(states, "is_cuda") or states.dtype != imgs.dtype or states.device != imgs.device or tuple(states.shape) != tuple(imgs.shape[1:]):
+        raise ValueError("nearest_image takes states as a uint8 tensor of the shape and device of guides")
+    if states.numel() and int(states.max()) >= int(N):
+        raise ValueError(f"nearest_image: an entry of states is >= N = {int(N)}")
+    return _nearest(int(N), states, imgs)
+
+
+def _pool_args(N, n, rounds, min_dist, partner_seed):
+    """(min_dist, the shifts s_k of the rounds) of relink_pool / relink_pool_host, and their refusals."""
+    if int(rounds) < 1:
+        raise ValueError(f"rounds must be >= 1, got {rounds}")
+    if n < 2:
+        raise ValueError(f"relink_pool needs a pool of at least 2 placements, got {n}")
+    N = int(N)
+    md = max(1, N * N // 8) if min_dist is None else int(min_dist)
+    rs = np.random.RandomState(int(partner_seed))
+    return md, [int(rs.randint(1, n)) for _ in range(int(rounds))]
+
+
+def relink_pool_host(N, states, seeds, rounds, min_dist=None, local_search="pairs", align=True, partner_seed=0):
+    """relink_pool in NumPy over relink_host: the same pool, energies and counts, no GPU."""
+    s = _host_states(N, states)
+    n = s.shape[0]
+    md, shifts = _pool_args(N, n, rounds, min_dist, partner_seed)
+    if abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH_PAIRS:
+        s = np.minimum(s, np.uint8(int(N) - 1))
+    sd = _hop_seeds(seeds, n)
+    pool, energy, n_replaced, best = s.copy(), None, [], []
+    for k, shift in enumerate(shifts):
+        guides = np.roll(pool, shift, axis=0)
+        if align:
+            guides = _nearest(int(N), pool, np.stack(_images(int(N), guides.reshape(-1, int(N), int(N)))).reshape(N_IMAGES, n, -1))[0]
+        r = relink_host(N, pool, guides, sd, min_dist=md, local_search=local_search, walk=k)
+        better = r["energy_out"] < r["energy_in"]
+        pool = np.where(better[:, None], r["state"], pool)
+        energy = np.where(better, r["energy_out"], r["energy_in"]).astype(np.int32)
+        n_replaced.append(int(better.sum()))
+        best.append(int(energy.min()))
+    return {"state": pool, "energy": energy, "n_replaced": np.array(n_replaced, dtype=np.int64), "best_energy": np.array(best, dtype=np.int32)}
+
+
+def relink_pool(N, states, seeds, rounds, min_dist=None, local_search="pairs", align=True, partner_seed=0, stream=None):
+    """Rounds of path relinking over a pool of board placements on the GPU: `states` is a torch uint8 tensor [n][N*N] on the device
+    (n >= 2; bytes >= N are clamped to N - 1 first), `seeds` an int32 or uint32 tensor [n].  Round k = 0 .. rounds - 1 takes as the
+    guide of slot r the placement of slot (r - s_k) mod n (torch.roll by s_k, drawn from 1 .. n - 1 with
+    np.random.RandomState(partner_seed), one draw per round), with align=True its image closest to the slot's placement (nearest_image),
+    and calls relink_device with walk = k and min_dist (default max(1, N^2 / 8)).  A slot takes the call's `state` when its energy_out
+    is strictly below the slot's own energy; otherwise it keeps its placement.  Everything stays on the device, on `stream` (default:
+    torch's current stream), with one synchronisation at the end.  Returns a dict: `state` uint8[n][N*N] and `energy` int32[n], tensors;
+    `n_replaced` int64[rounds] and `best_energy` int32[rounds] (the pool's smallest energy behind each round), NumPy arrays."""
+    import torch
+
+    n = _device_states("relink_pool", N, states)
+    md, shifts = _pool_args(N, n, rounds, min_dist, partner_seed)
+    N = int(N)
+    dev = states.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        pool = states.clamp(max=N - 1) if abi.MIN_N <= N <= abi.MAX_N_QUENCH_PAIRS else states
+        energy, n_replaced, best = None, [], []
+        for k, shift in enumerate(shifts):
+            guides = torch.roll(pool, shift, 0)
+            if align:
+                guides = _nearest(N, pool, torch.stack(_images(N, guides.reshape(-1, N, N))).reshape(N_IMAGES, n, -1))[0]
+            r = relink_device(N, pool, guides, seeds, min_dist=md, local_search=local_search, walk=k, stream=st)
+            better = r["energy_out"] < r["energy_in"]
+            pool = torch.where(better.unsqueeze(1), r["state"], pool)
+            energy = torch.where(better, r["energy_out"], r["energy_in"])
+            n_replaced.append(better.sum())
+            best.append(energy.min())
+        n_replaced, best = torch.stack(n_replaced), torch.stack(best)
+        st.synchronize()
+    return {"state": pool, "energy": energy, "n_replaced": n_replaced.cpu().numpy().astype(np.int64), "best_energy": best.cpu().numpy().astype(np.int32)}
 
 
 def check_mode(quench, N, board=True):
