@@ -3,6 +3,7 @@
 There is deliberately no CPU fallback: if the library is missing or no GPU is present the
 calls raise.  (The CPU oracle under oracle/ is test infrastructure and is never imported here.)
 """
+import collections
 import ctypes as C
 import importlib.util
 import os
@@ -103,6 +104,28 @@ def destroy_stream(handle):
     fn(C.c_void_p(handle))
 
 
+Feature = collections.namedtuple("Feature", "struct prefix entries")
+# What sits next to the sweep, one row per feature: the parameter block of include/mcq.h, the prefix of its own error text
+# (mcq_<prefix>_last_error) and its entry points.  An entry `x` is the C function mcq_x -- (struct*) when it ends in _host, (struct*,
+# hipStream_t) otherwise -- and the callable x of this module.  lib() declares them and the loop below the table makes the callables.
+# (The mcq_resample_* calls of population annealing have signatures of their own and are written out.)
+FEATURES = {
+    "population": Feature(abi.Resample, "population", ()),
+    "quench": Feature(abi.Quench, "quench", ("quench_host", "quench_device")),
+    "quench_pairs": Feature(abi.QuenchPairs, "quench_pairs", ("quench_pairs_host", "quench_pairs_device")),
+    "hop": Feature(abi.Hop, "hop", ("hop_host", "hop_device")),
+    "hop3d": Feature(abi.Hop3d, "hop3d", ("hop3d_host", "hop3d_device")),
+    "tabu": Feature(abi.Tabu, "tabu", ("tabu_host", "tabu_device")),
+    "tabu3d": Feature(abi.Tabu3d, "tabu3d", ("tabu3d_host", "tabu3d_device")),
+    "relink": Feature(abi.Relink, "relink", ("relink_host", "relink_device")),
+    "quench3d": Feature(abi.Quench3D, "quench3d", ("quench3d_host", "quench3d_device")),
+    "heatbath": Feature(abi.Heatbath, "heatbath", ("heatbath_host", "heatbath_device", "heatbath_counters_device")),
+    "heatbath3d": Feature(abi.Heatbath3D, "heatbath3d", ("heatbath3d_host", "heatbath3d_device")),
+    "temper": Feature(abi.Temper, "temper", ("temper_host", "temper_device", "temper_counters_device")),
+    "temper3d": Feature(abi.Temper3D, "temper3d", ("temper3d_host", "temper3d_device")),
+}
+
+
 def lib():
     """Load csrc/libmcq_hip.so (building it if the sources are newer and hipcc exists)."""
     global _lib
@@ -173,380 +196,64 @@ def lib():
         L.mcq_checkpoint_device.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Outputs), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.mcq_run_host_from.restype = C.c_int
         L.mcq_run_host_from.argtypes = [C.POINTER(abi.Params), C.POINTER(abi.Resume), C.c_void_p, C.POINTER(abi.Outputs), C.c_void_p, C.POINTER(C.c_double)]
-        L.mcq_population_last_error.restype = C.c_char_p
         L.mcq_resample_scratch_bytes.restype = C.c_size_t
         L.mcq_resample_scratch_bytes.argtypes = [C.POINTER(abi.Resample)]
         L.mcq_resample_device.restype = C.c_int
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
-        L.mcq_quench_last_error.restype = C.c_char_p
-        L.mcq_quench_device.restype = C.c_int
-        L.mcq_quench_device.argtypes = [C.POINTER(abi.Quench), C.c_void_p]
-        L.mcq_quench_host.restype = C.c_int
-        L.mcq_quench_host.argtypes = [C.POINTER(abi.Quench)]
-        L.mcq_heatbath_last_error.restype = C.c_char_p
-        L.mcq_heatbath_device.restype = C.c_int
-        L.mcq_heatbath_device.argtypes = [C.POINTER(abi.Heatbath), C.c_void_p]
-        L.mcq_heatbath_counters_device.restype = C.c_int
-        L.mcq_heatbath_counters_device.argtypes = [C.POINTER(abi.Heatbath), C.c_void_p]
-        L.mcq_heatbath_host.restype = C.c_int
-        L.mcq_heatbath_host.argtypes = [C.POINTER(abi.Heatbath)]
-        L.mcq_quench3d_last_error.restype = C.c_char_p
-        L.mcq_quench3d_device.restype = C.c_int
-        L.mcq_quench3d_device.argtypes = [C.POINTER(abi.Quench3D), C.c_void_p]
-        L.mcq_quench3d_host.restype = C.c_int
-        L.mcq_quench3d_host.argtypes = [C.POINTER(abi.Quench3D)]
-        L.mcq_heatbath3d_last_error.restype = C.c_char_p
-        L.mcq_heatbath3d_device.restype = C.c_int
-        L.mcq_heatbath3d_device.argtypes = [C.POINTER(abi.Heatbath3D), C.c_void_p]
-        L.mcq_heatbath3d_host.restype = C.c_int
-        L.mcq_heatbath3d_host.argtypes = [C.POINTER(abi.Heatbath3D)]
-        L.mcq_temper_last_error.restype = C.c_char_p
-        L.mcq_temper_device.restype = C.c_int
-        L.mcq_temper_device.argtypes = [C.POINTER(abi.Temper), C.c_void_p]
-        L.mcq_temper_counters_device.restype = C.c_int
-        L.mcq_temper_counters_device.argtypes = [C.POINTER(abi.Temper), C.c_void_p]
-        L.mcq_temper_host.restype = C.c_int
-        L.mcq_temper_host.argtypes = [C.POINTER(abi.Temper)]
-        L.mcq_temper3d_last_error.restype = C.c_char_p
-        L.mcq_temper3d_device.restype = C.c_int
-        L.mcq_temper3d_device.argtypes = [C.POINTER(abi.Temper3D), C.c_void_p]
-        L.mcq_temper3d_host.restype = C.c_int
-        L.mcq_temper3d_host.argtypes = [C.POINTER(abi.Temper3D)]
-        L.mcq_quench_pairs_last_error.restype = C.c_char_p
-        L.mcq_quench_pairs_device.restype = C.c_int
-        L.mcq_quench_pairs_device.argtypes = [C.POINTER(abi.QuenchPairs), C.c_void_p]
-        L.mcq_quench_pairs_host.restype = C.c_int
-        L.mcq_quench_pairs_host.argtypes = [C.POINTER(abi.QuenchPairs)]
-        L.mcq_hop_last_error.restype = C.c_char_p
-        L.mcq_hop_device.restype = C.c_int
-        L.mcq_hop_device.argtypes = [C.POINTER(abi.Hop), C.c_void_p]
-        L.mcq_hop_host.restype = C.c_int
-        L.mcq_hop_host.argtypes = [C.POINTER(abi.Hop)]
-        L.mcq_hop3d_last_error.restype = C.c_char_p
-        L.mcq_hop3d_device.restype = C.c_int
-        L.mcq_hop3d_device.argtypes = [C.POINTER(abi.Hop3d), C.c_void_p]
-        L.mcq_hop3d_host.restype = C.c_int
-        L.mcq_hop3d_host.argtypes = [C.POINTER(abi.Hop3d)]
-        L.mcq_tabu_last_error.restype = C.c_char_p
-        L.mcq_tabu_device.restype = C.c_int
-        L.mcq_tabu_device.argtypes = [C.POINTER(abi.Tabu), C.c_void_p]
-        L.mcq_tabu_host.restype = C.c_int
-        L.mcq_tabu_host.argtypes = [C.POINTER(abi.Tabu)]
-        L.mcq_tabu3d_last_error.restype = C.c_char_p
-        L.mcq_tabu3d_device.restype = C.c_int
-        L.mcq_tabu3d_device.argtypes = [C.POINTER(abi.Tabu3d), C.c_void_p]
-        L.mcq_tabu3d_host.restype = C.c_int
-        L.mcq_tabu3d_host.argtypes = [C.POINTER(abi.Tabu3d)]
-        L.mcq_relink_last_error.restype = C.c_char_p
-        L.mcq_relink_device.restype = C.c_int
-        L.mcq_relink_device.argtypes = [C.POINTER(abi.Relink), C.c_void_p]
-        L.mcq_relink_host.restype = C.c_int
-        L.mcq_relink_host.argtypes = [C.POINTER(abi.Relink)]
+        for f in FEATURES.values():
+            getattr(L, f"mcq_{f.prefix}_last_error").restype = C.c_char_p
+            for name in f.entries:  # (struct*) for a host entry, (struct*, hipStream_t) for a device entry
+                fn = getattr(L, "mcq_" + name)
+                fn.restype = C.c_int
+                fn.argtypes = [C.POINTER(f.struct)] + ([] if name.endswith("_host") else [C.c_void_p])
         if L.mcq_abi_version() != abi.ABI_VERSION:
             raise McqError("libmcq_hip.so ABI version mismatch; rebuild")
         _lib = L
     return _lib
 
 
-def _check(rc):
+def _raise(rc, last_error):
+    """Nothing for abi.OK; otherwise the exception of a return code, with the text `last_error()` holds: the library keeps one
+    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES), and a call's text is read from its own."""
     if rc == abi.OK:
         return
-    msg = lib().mcq_last_error().decode(errors="replace")
+    msg = last_error().decode(errors="replace")
     if rc == abi.EINVAL:
         raise ValueError(msg)
     if rc == abi.ENOMEM:
         raise MemoryError(msg)
     raise McqError(msg)
+
+
+def _check(rc):
+    _raise(rc, lib().mcq_last_error)
 
 
 def _check_population(rc):
     """_check for the mcq_resample_* calls, which keep their own message (mcq_population_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_population_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def _check_quench(rc):
-    """_check for the mcq_quench_* calls, which keep their own message (mcq_quench_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_quench_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def _check_heatbath(rc):
-    """_check for the mcq_heatbath_* calls, which keep their own message (mcq_heatbath_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_heatbath_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def heatbath_host(q):
-    """mcq_heatbath_host on a filled abi.Heatbath block of HOST pointers.  Pure host code, no GPU."""
-    _check_heatbath(lib().mcq_heatbath_host(C.byref(q)))
-
-
-def heatbath_device(q, stream):
-    """mcq_heatbath_device on a filled abi.Heatbath block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_heatbath(lib().mcq_heatbath_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def heatbath_counters_device(q, stream):
-    """mcq_heatbath_counters_device (the counter form, N <= abi.MAX_N_HEATBATH_COUNTERS) on a filled abi.Heatbath block of DEVICE pointers,
-    enqueued on the torch stream `stream`; asynchronous."""
-    _check_heatbath(lib().mcq_heatbath_counters_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def quench_host(q):
-    """mcq_quench_host on a filled abi.Quench block of HOST pointers.  Pure host code, no GPU."""
-    _check_quench(lib().mcq_quench_host(C.byref(q)))
-
-
-def quench_device(q, stream):
-    """mcq_quench_device on a filled abi.Quench block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_quench(lib().mcq_quench_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_quench_pairs(rc):
-    """_check for the mcq_quench_pairs_* calls, which keep their own message (mcq_quench_pairs_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_quench_pairs_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def quench_pairs_host(q):
-    """mcq_quench_pairs_host on a filled abi.QuenchPairs block of HOST pointers.  Pure host code, no GPU."""
-    _check_quench_pairs(lib().mcq_quench_pairs_host(C.byref(q)))
-
-
-def quench_pairs_device(q, stream):
-    """mcq_quench_pairs_device on a filled abi.QuenchPairs block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_quench_pairs(lib().mcq_quench_pairs_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_hop(rc):
-    """_check for the mcq_hop_* calls, which keep their own message (mcq_hop_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_hop_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def hop_host(q):
-    """mcq_hop_host on a filled abi.Hop block of HOST pointers.  Pure host code, no GPU."""
-    _check_hop(lib().mcq_hop_host(C.byref(q)))
-
-
-def hop_device(q, stream):
-    """mcq_hop_device on a filled abi.Hop block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_hop(lib().mcq_hop_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_hop3d(rc):
-    """_check for the mcq_hop3d_* calls, which keep their own message (mcq_hop3d_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_hop3d_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def hop3d_host(q):
-    """mcq_hop3d_host on a filled abi.Hop3d block of HOST pointers.  Pure host code, no GPU."""
-    _check_hop3d(lib().mcq_hop3d_host(C.byref(q)))
-
-
-def hop3d_device(q, stream):
-    """mcq_hop3d_device on a filled abi.Hop3d block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_hop3d(lib().mcq_hop3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_tabu(rc):
-    """_check for the mcq_tabu_* calls, which keep their own message (mcq_tabu_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_tabu_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def tabu_host(q):
-    """mcq_tabu_host on a filled abi.Tabu block of HOST pointers.  Pure host code, no GPU."""
-    _check_tabu(lib().mcq_tabu_host(C.byref(q)))
-
-
-def tabu_device(q, stream):
-    """mcq_tabu_device on a filled abi.Tabu block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_tabu(lib().mcq_tabu_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_tabu3d(rc):
-    """_check for the mcq_tabu3d_* calls, which keep their own message (mcq_tabu3d_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_tabu3d_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def tabu3d_host(q):
-    """mcq_tabu3d_host on a filled abi.Tabu3d block of HOST pointers.  Pure host code, no GPU."""
-    _check_tabu3d(lib().mcq_tabu3d_host(C.byref(q)))
-
-
-def tabu3d_device(q, stream):
-    """mcq_tabu3d_device on a filled abi.Tabu3d block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_tabu3d(lib().mcq_tabu3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_relink(rc):
-    """_check for the mcq_relink_* calls, which keep their own message (mcq_relink_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_relink_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def relink_host(q):
-    """mcq_relink_host on a filled abi.Relink block of HOST pointers.  Pure host code, no GPU."""
-    _check_relink(lib().mcq_relink_host(C.byref(q)))
-
-
-def relink_device(q, stream):
-    """mcq_relink_device on a filled abi.Relink block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_relink(lib().mcq_relink_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_quench3d(rc):
-    """_check for the mcq_quench3d_* calls, which keep their own message (mcq_quench3d_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_quench3d_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def quench3d_host(q):
-    """mcq_quench3d_host on a filled abi.Quench3D block of HOST pointers.  Pure host code, no GPU."""
-    _check_quench3d(lib().mcq_quench3d_host(C.byref(q)))
-
-
-def quench3d_device(q, stream):
-    """mcq_quench3d_device on a filled abi.Quench3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_quench3d(lib().mcq_quench3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_heatbath3d(rc):
-    """_check for the mcq_heatbath3d_* calls, which keep their own message (mcq_heatbath3d_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_heatbath3d_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def heatbath3d_host(q):
-    """mcq_heatbath3d_host on a filled abi.Heatbath3D block of HOST pointers.  Pure host code, no GPU."""
-    _check_heatbath3d(lib().mcq_heatbath3d_host(C.byref(q)))
-
-
-def heatbath3d_device(q, stream):
-    """mcq_heatbath3d_device on a filled abi.Heatbath3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_heatbath3d(lib().mcq_heatbath3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_temper(rc):
-    """_check for the mcq_temper_* calls, which keep their own message (mcq_temper_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_temper_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def temper_host(q):
-    """mcq_temper_host on a filled abi.Temper block of HOST pointers.  Pure host code, no GPU."""
-    _check_temper(lib().mcq_temper_host(C.byref(q)))
-
-
-def temper_device(q, stream):
-    """mcq_temper_device on a filled abi.Temper block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_temper(lib().mcq_temper_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def temper_counters_device(q, stream):
-    """mcq_temper_counters_device (the counter form, N <= abi.MAX_N_TEMPER_COUNTERS) on a filled abi.Temper block of DEVICE pointers,
-    enqueued on the torch stream `stream`; asynchronous."""
-    _check_temper(lib().mcq_temper_counters_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
-
-
-def _check_temper3d(rc):
-    """_check for the mcq_temper3d_* calls, which keep their own message (mcq_temper3d_last_error)."""
-    if rc == abi.OK:
-        return
-    msg = lib().mcq_temper3d_last_error().decode(errors="replace")
-    if rc == abi.EINVAL:
-        raise ValueError(msg)
-    if rc == abi.ENOMEM:
-        raise MemoryError(msg)
-    raise McqError(msg)
-
-
-def temper3d_host(q):
-    """mcq_temper3d_host on a filled abi.Temper3D block of HOST pointers.  Pure host code, no GPU."""
-    _check_temper3d(lib().mcq_temper3d_host(C.byref(q)))
-
-
-def temper3d_device(q, stream):
-    """mcq_temper3d_device on a filled abi.Temper3D block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."""
-    _check_temper3d(lib().mcq_temper3d_device(C.byref(q), C.c_void_p(stream.cuda_stream)))
+    _raise(rc, lib().mcq_population_last_error)
+
+
+def _entry(feature, name):
+    """The callable of one entry of FEATURES: (q) for a host entry, (q, stream) with a torch stream for a device entry."""
+    last_error, struct = f"mcq_{feature.prefix}_last_error", feature.struct.__name__
+    if name.endswith("_host"):
+        def call(q):
+            _raise(getattr(lib(), "mcq_" + name)(C.byref(q)), getattr(lib(), last_error))
+        call.__doc__ = f"mcq_{name} on a filled abi.{struct} block of HOST pointers.  Pure host code, no GPU."
+    else:
+        def call(q, stream):
+            _raise(getattr(lib(), "mcq_" + name)(C.byref(q), C.c_void_p(stream.cuda_stream)), getattr(lib(), last_error))
+        call.__doc__ = f"mcq_{name} on a filled abi.{struct} block of DEVICE pointers, enqueued on the torch stream `stream`; asynchronous."
+    call.__name__ = call.__qualname__ = name
+    return call
+
+
+for _feature in FEATURES.values():
+    for _name in _feature.entries:
+        globals()[_name] = _entry(_feature, _name)
 
 
 def resample_plan_host(energies, population, table, offsets):

@@ -38,6 +38,8 @@ tabu_queens, tabu_queens_device and tabu_queens_host walk on from a full_3d plac
 the best admissible move of a conflicting queen to a free cell in every iteration, also when it raises the energy, with the cell left
 forbidden for a while.  A whole run is one launch.  Opt-in like everything here.
 """
+import collections
+
 import numpy as np
 
 from . import _lib, abi
@@ -117,31 +119,99 @@ def _device_out(out, states):
     return out
 
 
-def _device_outputs(q, states, out, dtypes, conflicts):
-    """The result tensors of a quench on the device, from a *_DTYPES table -- int32 per chain, and `conflicts` int16 of the shape given
-    (None: left out) --, with the block `q` pointed at them and at `states`.  `out` is _device_out's."""
+# One search of this module: `block` builds its parameter block from (N, n_chains, ...) -- (N, Q, n_chains, ...) for full_3d --, `dtypes`
+# is its *_DTYPES table, `host` and `device` are its entries in _lib, `like` names the placements it returns next to `state`, and
+# `seeds` says whether it draws (a seed per chain and a history stride in the block).
+_Search = collections.namedtuple("_Search", "block dtypes host device like seeds")
+# the outputs with a row per chain, which a caller turns on: a call allocates those it is given a shape for
+_ROWS = ("conflicts", "energy_hist", "tabu_out")
+_QUENCH = _Search(_block, abi.QUENCH_DTYPES, _lib.quench_host, _lib.quench_device, (), False)
+
+
+def _skip(d, shapes, figures):
+    """The fields of d.dtypes a call leaves out: the rows without a shape, and with figures=False everything else as well."""
+    return tuple(k for k in d.dtypes if k not in shapes and (k in _ROWS or not figures))
+
+
+def _check_seeds(fn, seeds, n, dev):
+    """ValueError unless `seeds` is what the device wrapper `fn` of a search takes: the seeds' 32 bits, whatever the sign."""
     import torch
 
-    res = {"state": _device_out(out, states)}
-    for k in dtypes:
-        if k != "conflicts":
-            res[k] = torch.empty(int(states.shape[0]), dtype=torch.int32, device=states.device)
-        elif conflicts is not None:
-            res[k] = torch.empty(conflicts, dtype=torch.int16, device=states.device)
-    q.state_in, q.state_out = states.data_ptr(), res["state"].data_ptr()
-    for k in dtypes:
-        if k in res:
-            setattr(q, k, res[k].data_ptr())
+    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
+            and tuple(seeds.shape) == (n,)):
+        raise ValueError(f"{fn} takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
+
+
+def _host_call(d, dims, s, args, shapes, seeds=None, width=0, inputs=None, figures=True):
+    """The search `d` in the library's host code on the placements `s` (_host_states, _host_queens): the seeds checked, the block from
+    d.block(*dims, n_chains, *args), _host_outputs with the rows `shapes` names, and the call.  `inputs` (optional) is called behind the
+    seeds' check and gives {field: array} of what else the block points at; `width` is the history stride.  Returns the outputs."""
+    n = s.shape[0]
+    if d.seeds:
+        seeds = _hop_seeds(seeds, n)
+    q = d.block(*dims, n, *args)
+    out = _host_outputs(q, s, d.dtypes, shapes, _skip(d, shapes, figures), like=d.like if figures else ())
+    keep = dict(inputs() if inputs else {}, **({"seeds": seeds} if d.seeds else {}))  # referenced until the library has returned
+    for k, a in keep.items():
+        setattr(q, k, a.ctypes.data)
+    if d.seeds:
+        q.hist_stride = width
+    d.host(q)
+    return out
+
+
+def _device_call(d, fn, dims, n, states, args, shapes, seeds=None, width=0, inputs=None, figures=True, out=None, stream=None):
+    """The search `d` enqueued for the device wrapper `fn` on the checked tensor `states` of n chains, on `stream` (default: torch's
+    current stream) and the device of states: _host_call's steps with tensors -- `state` is _device_out's, a field of d.dtypes gets the
+    signed torch type of its width --, and nothing is copied back or waited for.  Returns the dict of result tensors."""
+    import torch
+
+    dev = states.device
+    if d.seeds:
+        _check_seeds(fn, seeds, n, dev)
+    ins = dict(inputs() if inputs else {}, **({"seeds": seeds} if d.seeds else {}))
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    tdt = {np.int32: torch.int32, np.int64: torch.int64, np.uint16: torch.int16}
+    skip = _skip(d, shapes, figures)
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        q = d.block(*dims, n, *args)
+        res = {"state": _device_out(out, states)}
+        for k in d.like if figures else ():
+            res[k] = torch.empty_like(states)
+        for k, dt in d.dtypes.items():
+            if k not in skip:
+                res[k] = torch.empty(shapes.get(k, n), dtype=tdt[dt], device=dev)
+        q.state_in, q.state_out = states.data_ptr(), res["state"].data_ptr()
+        for k, t in list(res.items())[1:] + list(ins.items()):
+            setattr(q, k, t.data_ptr())
+        if d.seeds:
+            q.hist_stride = width
+        d.device(q, st)
     return res
+
+
+def _round_trip(d, dims, args, s, arrays, call):
+    """What the NumPy wrappers of the device searches share: no chain is refused by the library's host entry, the placements `s` and the
+    host arrays `arrays()` gives (None stays None) go to the current device, `call` hands them to the device wrapper, the stream is
+    waited for and the results come back as NumPy arrays, the placements in the shape of s."""
+    import torch
+
+    if s.shape[0] == 0:
+        d.host(d.block(*dims, 0, *args))  # raises the library's refusal
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = call(*(None if a is None else torch.from_numpy(a).to(dev) for a in (s,) + tuple(arrays())))
+    torch.cuda.current_stream(dev).synchronize()
+    out = (tabu_to_numpy if "tabu_out" in d.dtypes else to_numpy)(res)
+    for k in ("state",) + d.like:
+        if k in out:
+            out[k] = out[k].reshape(s.shape)
+    return out
 
 
 def quench_states_host(N, states, max_passes=0, conflicts=True):
     """mcq_quench_host: the rule in the library's plain host code, NumPy in and out, no GPU.  Same result as quench_states."""
     s = _host_states(N, states)
-    q = _block(N, s.shape[0], max_passes)
-    out = _host_outputs(q, s, abi.QUENCH_DTYPES, {"conflicts": s.shape}, () if conflicts else ("conflicts",))
-    _lib.quench_host(q)
-    return out
+    return _host_call(_QUENCH, (N,), s, (max_passes,), {"conflicts": s.shape} if conflicts else {})
 
 
 def quench_device(N, states, max_passes=0, out=None, conflicts=True, stream=None):
@@ -151,16 +221,8 @@ def quench_device(N, states, max_passes=0, out=None, conflicts=True, stream=None
     default a new one.  Returns a dict of tensors: `state` uint8 like `states`, `energy_in` (the recount of the input), `energy_out`,
     `n_moves`, `n_passes` int32[n_chains] and, unless conflicts=False, `conflicts` int16[n_chains][N*N] (the uint16 counts a(c, h(c)) of the
     output; at most 4 (N - 1), so the sign bit is never set)."""
-    import torch
-
     n = _device_states("quench_device", N, states)
-    dev = states.device
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block(N, n, max_passes)
-        res = _device_outputs(q, states, out, abi.QUENCH_DTYPES, tuple(states.shape) if conflicts else None)
-        _lib.quench_device(q, st)
-    return res
+    return _device_call(_QUENCH, "quench_device", (N,), n, states, (max_passes,), {"conflicts": tuple(states.shape)} if conflicts else {}, out=out, stream=stream)
 
 
 def quench_states(N, states, max_passes=0, conflicts=True):
@@ -170,15 +232,8 @@ def quench_states(N, states, max_passes=0, conflicts=True):
     `energy_out`, `n_moves`, `n_passes` int32[n_chains], and `conflicts` uint16[n_chains][N*N], the number of queens attacking each
     column's queen in the output (its sum is 2 energy_out).  A placement with n_moves == 0 was a local minimum already.
     ValueError for what the library refuses (N outside 2 .. 128, no chain, a negative max_passes)."""
-    import torch
-
-    s = _host_states(N, states)
-    if s.shape[0] == 0:
-        _lib.quench_host(_block(N, 0, max_passes))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res = quench_device(N, torch.from_numpy(s).to(dev), max_passes=max_passes, conflicts=conflicts)
-    torch.cuda.current_stream(dev).synchronize()
-    return to_numpy(res)
+    return _round_trip(_QUENCH, (N,), (max_passes,), _host_states(N, states), lambda: (),
+                       lambda t: quench_device(N, t, max_passes=max_passes, conflicts=conflicts))
 
 
 def to_numpy(res):
@@ -198,14 +253,14 @@ def _block_pairs(N, n, max_rounds):
     return q
 
 
+_PAIRS = _Search(_block_pairs, abi.QUENCH_PAIRS_DTYPES, _lib.quench_pairs_host, _lib.quench_pairs_device, (), False)
+
+
 def quench_pairs_host(N, states, max_rounds=0, conflicts=True):
     """mcq_quench_pairs_host: the pair-move rule in the library's plain host code, NumPy in and out, no GPU.  Same result as
     quench_pairs."""
     s = _host_states(N, states)
-    q = _block_pairs(N, s.shape[0], max_rounds)
-    out = _host_outputs(q, s, abi.QUENCH_PAIRS_DTYPES, {"conflicts": s.shape}, () if conflicts else ("conflicts",))
-    _lib.quench_pairs_host(q)
-    return out
+    return _host_call(_PAIRS, (N,), s, (max_rounds,), {"conflicts": s.shape} if conflicts else {})
 
 
 def quench_pairs_device(N, states, max_rounds=0, out=None, conflicts=True, stream=None):
@@ -215,16 +270,8 @@ def quench_pairs_device(N, states, max_rounds=0, out=None, conflicts=True, strea
     tensors: `state` uint8 like `states`; `energy_in`, `energy_single` (E after the first single-move descent: quench_device's
     energy_out), `energy_out`, `n_moves` (single moves of all descents), `n_pair_moves`, `n_rounds` (scans), `certified` int32[n_chains];
     and, unless conflicts=False, `conflicts` int16[n_chains][N*N]."""
-    import torch
-
     n = _device_states("quench_pairs_device", N, states)
-    dev = states.device
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block_pairs(N, n, max_rounds)
-        res = _device_outputs(q, states, out, abi.QUENCH_PAIRS_DTYPES, tuple(states.shape) if conflicts else None)
-        _lib.quench_pairs_device(q, st)
-    return res
+    return _device_call(_PAIRS, "quench_pairs_device", (N,), n, states, (max_rounds,), {"conflicts": tuple(states.shape)} if conflicts else {}, out=out, stream=stream)
 
 
 def quench_pairs(N, states, max_rounds=0, conflicts=True):
@@ -234,15 +281,8 @@ def quench_pairs(N, states, max_rounds=0, conflicts=True):
     applied a move (certified = 0; the output is still a single-move minimum).  Returns a dict of NumPy arrays with the fields of
     FIELDS_PAIRS; a placement with n_pair_moves == 0 and n_moves == 0 was a 2-move minimum already.  ValueError for what the library
     refuses (N outside 2 .. 32, no chain, a negative max_rounds)."""
-    import torch
-
-    s = _host_states(N, states)
-    if s.shape[0] == 0:
-        _lib.quench_pairs_host(_block_pairs(N, 0, max_rounds))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res = quench_pairs_device(N, torch.from_numpy(s).to(dev), max_rounds=max_rounds, conflicts=conflicts)
-    torch.cuda.current_stream(dev).synchronize()
-    return to_numpy(res)
+    return _round_trip(_PAIRS, (N,), (max_rounds,), _host_states(N, states), lambda: (),
+                       lambda t: quench_pairs_device(N, t, max_rounds=max_rounds, conflicts=conflicts))
 
 
 FIELDS_HOP = ("state", "energy_in", "energy_start", "energy_out", "best_energy", "best_hop", "best_state", "n_accepted", "n_improved", "n_moves",
@@ -258,6 +298,9 @@ def _block_hop(N, n, n_hops, kick, slack, local_search, first_hop):
     return q
 
 
+_HOP = _Search(_block_hop, abi.HOP_DTYPES, _lib.hop_host, _lib.hop_device, ("best_state",), True)
+
+
 def _hop_seeds(seeds, n):
     s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
     if s.shape[0] != n:
@@ -268,14 +311,8 @@ def _hop_seeds(seeds, n):
 def hop_host(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, hist=False):
     """mcq_hop_host: basin hopping in the library's plain host code, NumPy in and out, no GPU.  Same result as hop_states."""
     s = _host_states(N, states)
-    n = s.shape[0]
-    sd = _hop_seeds(seeds, n)
-    q = _block_hop(N, n, n_hops, kick, slack, local_search, first_hop)
-    width = max(int(n_hops), 0) + 1
-    out = _host_outputs(q, s, abi.HOP_DTYPES, {"energy_hist": (n, width)}, () if hist else ("energy_hist",), like=("best_state",))
-    q.seeds, q.hist_stride = sd.ctypes.data, width
-    _lib.hop_host(q)
-    return out
+    n, width = s.shape[0], max(int(n_hops), 0) + 1
+    return _host_call(_HOP, (N,), s, (n_hops, kick, slack, local_search, first_hop), {"energy_hist": (n, width)} if hist else {}, seeds, width)
 
 
 def hop_device(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, hist=False, out=None, stream=None):
@@ -286,29 +323,9 @@ def hop_device(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", 
     the fields of FIELDS_HOP: `state` and `best_state` uint8 like `states`; `energy_in`, `energy_start`, `energy_out`, `best_energy`
     int32[n_chains]; `best_hop`, `n_accepted`, `n_improved`, `n_moves`, `n_pair_moves` int64[n_chains]; and with hist=True `energy_hist`
     int32[n_chains][n_hops + 1]."""
-    import torch
-
-    n = _device_states("hop_device", N, states)
-    dev = states.device
-    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
-            and tuple(seeds.shape) == (n,)):
-        raise ValueError(f"hop_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block_hop(N, n, n_hops, kick, slack, local_search, first_hop)
-        width = max(int(n_hops), 0) + 1
-        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
-        for k, dt in abi.HOP_DTYPES.items():
-            if k != "energy_hist":
-                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
-            elif hist:
-                res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
-        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
-        for k in abi.HOP_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
-        _lib.hop_device(q, st)
-    return res
+    n, width = _device_states("hop_device", N, states), max(int(n_hops), 0) + 1
+    return _device_call(_HOP, "hop_device", (N,), n, states, (n_hops, kick, slack, local_search, first_hop), {"energy_hist": (n, width)} if hist else {},
+                        seeds, width, out=out, stream=stream)
 
 
 def hop_states(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", first_hop=0, hist=False):
@@ -322,17 +339,10 @@ def hop_states(N, states, seeds, n_hops, kick=2, slack=0, local_search="pairs", 
     before that piece; n_improved of the whole is the number of new lows of the joined energy_hist (a piece counts against its own
     start, which with slack > 0 may lie above an earlier piece's best_energy).  ValueError for what the library refuses (N outside 2 .. 32, no chain, kick outside 1 .. 1024, a negative
     n_hops, first_hop or slack)."""
-    import torch
-
     s = _host_states(N, states)
     sd = _hop_seeds(seeds, s.shape[0])
-    if s.shape[0] == 0:
-        _lib.hop_host(_block_hop(N, 0, n_hops, kick, slack, local_search, first_hop))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res = hop_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_hops, kick=kick, slack=slack,
-                     local_search=local_search, first_hop=first_hop, hist=hist)
-    torch.cuda.current_stream(dev).synchronize()
-    return to_numpy(res)
+    return _round_trip(_HOP, (N,), (n_hops, kick, slack, local_search, first_hop), s, lambda: (sd.view(np.int32),),
+                       lambda t, ts: hop_device(N, t, ts, n_hops, kick=kick, slack=slack, local_search=local_search, first_hop=first_hop, hist=hist))
 
 
 def check_hops(hops, hop_kick, N, board=True):
@@ -360,33 +370,54 @@ def _block_tabu(N, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter):
     return q
 
 
-def _tabu_skip(hist, tabu_out):
-    return (() if hist else ("energy_hist",)) + (() if tabu_out else ("tabu_out",))
+_TABU = _Search(_block_tabu, abi.TABU_DTYPES, _lib.tabu_host, _lib.tabu_device, ("best_state",), True)
+
+
+def _tabu_shapes(n, width, cube, hist, tabu_out):
+    """The rows a tabu call was asked for: the history and the stamps."""
+    return dict({"energy_hist": (n, width)} if hist else {}, **({"tabu_out": (n, cube)} if tabu_out else {}))
+
+
+def _tabu_host_inputs(n, cube, tabu_in, best_floor):
+    """What an earlier piece of a run hands the host entry of a tabu search, as {field: array}; ValueError for another size."""
+    ins = {}
+    if tabu_in is not None:
+        ins["tabu_in"] = np.ascontiguousarray(tabu_in, dtype=np.uint16).reshape(-1)
+        if ins["tabu_in"].shape[0] != n * cube:
+            raise ValueError(f"tabu_in must be uint16[n_chains = {n}][N^3 = {cube}], got {np.shape(tabu_in)}")
+    if best_floor is not None:
+        ins["best_floor"] = np.ascontiguousarray(best_floor, dtype=np.int32).reshape(-1)
+        if ins["best_floor"].shape[0] != n:
+            raise ValueError(f"best_floor must be int32[n_chains = {n}], got {np.shape(best_floor)}")
+    return ins
+
+
+def _tabu_device_inputs(fn, n, cube, dev, tabu_in, best_floor):
+    """_tabu_host_inputs for the device wrapper `fn`: the tensors checked, nothing converted."""
+    import torch
+
+    if tabu_in is not None and not (isinstance(tabu_in, torch.Tensor) and tabu_in.device == dev and tabu_in.is_contiguous() and tabu_in.numel() == n * cube
+                                    and tabu_in.dtype in (torch.int16, getattr(torch, "uint16", torch.int16))):
+        raise ValueError(f"{fn} takes tabu_in as a contiguous int16 or uint16 tensor [n_chains = {n}][N^3 = {cube}] on the device of states")
+    if best_floor is not None and not (isinstance(best_floor, torch.Tensor) and best_floor.device == dev and best_floor.is_contiguous()
+                                       and best_floor.dtype == torch.int32 and tuple(best_floor.shape) == (n,)):
+        raise ValueError(f"{fn} takes best_floor as a contiguous int32 tensor [n_chains = {n}] on the device of states")
+    return {k: t for k, t in (("tabu_in", tabu_in), ("best_floor", best_floor)) if t is not None}
+
+
+def _tabu_arrays(sd, tabu_in, best_floor):
+    """The host arrays tabu_states and tabu_queens upload behind the placements: the seeds, the stamps and the floor, as the signed types."""
+    return (sd.view(np.int32), None if tabu_in is None else np.ascontiguousarray(tabu_in, dtype=np.uint16).view(np.int16),
+            None if best_floor is None else np.ascontiguousarray(best_floor, dtype=np.int32))
 
 
 def tabu_host(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None, hist=False,
               tabu_out=False):
     """mcq_tabu_host: tabu search in the library's plain host code, NumPy in and out, no GPU.  Same result as tabu_states."""
     s = _host_states(N, states)
-    n = s.shape[0]
-    sd = _hop_seeds(seeds, n)
-    q = _block_tabu(N, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
-    width, cube = max(int(n_iters), 0) + 1, s.shape[1] * max(int(N), 0)
-    out = _host_outputs(q, s, abi.TABU_DTYPES, {"energy_hist": (n, width), "tabu_out": (n, cube)}, _tabu_skip(hist, tabu_out), like=("best_state",))
-    q.seeds, q.hist_stride = sd.ctypes.data, width
-    keep = []
-    if tabu_in is not None:
-        keep.append(np.ascontiguousarray(tabu_in, dtype=np.uint16).reshape(-1))
-        if keep[-1].shape[0] != n * cube:
-            raise ValueError(f"tabu_in must be uint16[n_chains = {n}][N^3 = {cube}], got {np.shape(tabu_in)}")
-        q.tabu_in = keep[-1].ctypes.data
-    if best_floor is not None:
-        keep.append(np.ascontiguousarray(best_floor, dtype=np.int32).reshape(-1))
-        if keep[-1].shape[0] != n:
-            raise ValueError(f"best_floor must be int32[n_chains = {n}], got {np.shape(best_floor)}")
-        q.best_floor = keep[-1].ctypes.data
-    _lib.tabu_host(q)
-    return out
+    n, width, cube = s.shape[0], max(int(n_iters), 0) + 1, s.shape[1] * max(int(N), 0)
+    return _host_call(_TABU, (N,), s, (n_iters, tenure, tenure_rand, tenure_conf, first_iter), _tabu_shapes(n, width, cube, hist, tabu_out), seeds, width,
+                      lambda: _tabu_host_inputs(n, cube, tabu_in, best_floor))
 
 
 def tabu_device(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None, hist=False,
@@ -399,44 +430,9 @@ def tabu_device(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf
     tensors with the fields of FIELDS_TABU: `state` and `best_state` uint8 like `states`; `energy_in`, `energy_out`, `best_energy`
     int32[n_chains]; `best_iter`, `n_moves`, `n_aspired`, `n_uphill`, `n_stalled` int64[n_chains]; with hist=True `energy_hist`
     int32[n_chains][n_iters + 1]; with tabu_out=True `tabu_out` int16[n_chains][N^3] (the uint16 stamps; to_numpy views them so)."""
-    import torch
-
-    n = _device_states("tabu_device", N, states)
-    dev = states.device
-    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
-            and tuple(seeds.shape) == (n,)):
-        raise ValueError(f"tabu_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
-    cube = int(states.shape[1]) * max(int(N), 0)
-    if tabu_in is not None and not (isinstance(tabu_in, torch.Tensor) and tabu_in.device == dev and tabu_in.is_contiguous() and tabu_in.numel() == n * cube
-                                    and tabu_in.dtype in (torch.int16, getattr(torch, "uint16", torch.int16))):
-        raise ValueError(f"tabu_device takes tabu_in as a contiguous int16 or uint16 tensor [n_chains = {n}][N^3 = {cube}] on the device of states")
-    if best_floor is not None and not (isinstance(best_floor, torch.Tensor) and best_floor.device == dev and best_floor.is_contiguous()
-                                       and best_floor.dtype == torch.int32 and tuple(best_floor.shape) == (n,)):
-        raise ValueError(f"tabu_device takes best_floor as a contiguous int32 tensor [n_chains = {n}] on the device of states")
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block_tabu(N, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
-        width = max(int(n_iters), 0) + 1
-        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
-        for k, dt in abi.TABU_DTYPES.items():
-            if k == "energy_hist":
-                if hist:
-                    res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
-            elif k == "tabu_out":
-                if tabu_out:
-                    res[k] = torch.empty((n, cube), dtype=torch.int16, device=dev)
-            else:
-                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
-        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
-        if tabu_in is not None:
-            q.tabu_in = tabu_in.data_ptr()
-        if best_floor is not None:
-            q.best_floor = best_floor.data_ptr()
-        for k in abi.TABU_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
-        _lib.tabu_device(q, st)
-    return res
+    n, width, cube = _device_states("tabu_device", N, states), max(int(n_iters), 0) + 1, int(states.shape[1]) * max(int(N), 0)
+    return _device_call(_TABU, "tabu_device", (N,), n, states, (n_iters, tenure, tenure_rand, tenure_conf, first_iter), _tabu_shapes(n, width, cube, hist, tabu_out),
+                        seeds, width, lambda: _tabu_device_inputs("tabu_device", n, cube, states.device, tabu_in, best_floor), out=out, stream=stream)
 
 
 def tabu_to_numpy(res):
@@ -459,19 +455,11 @@ def tabu_states(N, states, seeds, n_iters, tenure=10, tenure_rand=0, tenure_conf
     best_floor = the best_energy of the piece before; the counters of the pieces add up, and best_state / best_iter of the whole are
     those of the LAST piece with best_iter > 0.  ValueError for what the library refuses (N outside 2 .. 32, no chain, tenure outside
     0 .. 8192, tenure_rand outside 0 .. 4095, tenure_conf outside 0 .. 64, a negative n_iters or first_iter)."""
-    import torch
-
     s = _host_states(N, states)
     sd = _hop_seeds(seeds, s.shape[0])
-    if s.shape[0] == 0:
-        _lib.tabu_host(_block_tabu(N, 0, n_iters, tenure, tenure_rand, tenure_conf, first_iter))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    ti = None if tabu_in is None else torch.from_numpy(np.ascontiguousarray(tabu_in, dtype=np.uint16).view(np.int16)).to(dev)
-    bf = None if best_floor is None else torch.from_numpy(np.ascontiguousarray(best_floor, dtype=np.int32)).to(dev)
-    res = tabu_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_iters, tenure=tenure, tenure_rand=tenure_rand,
-                      tenure_conf=tenure_conf, first_iter=first_iter, tabu_in=ti, best_floor=bf, hist=hist, tabu_out=tabu_out)
-    torch.cuda.current_stream(dev).synchronize()
-    return tabu_to_numpy(res)
+    return _round_trip(_TABU, (N,), (n_iters, tenure, tenure_rand, tenure_conf, first_iter), s, lambda: _tabu_arrays(sd, tabu_in, best_floor),
+                       lambda t, ts, ti, bf: tabu_device(N, t, ts, n_iters, tenure=tenure, tenure_rand=tenure_rand, tenure_conf=tenure_conf, first_iter=first_iter,
+                                                         tabu_in=ti, best_floor=bf, hist=hist, tabu_out=tabu_out))
 
 
 def check_tabu(tabu_iters, tabu_tenure, hops, N, board=True):
@@ -508,23 +496,17 @@ def _relink_width(N, max_steps):
     return (int(max_steps) if int(max_steps) > 0 else max(int(N), 0) ** 2) + 1
 
 
-def _relink_skip(hist, figures):
-    return tuple(k for k in abi.RELINK_DTYPES if (k == "energy_hist" and not hist) or (k != "energy_hist" and not figures))
+_RELINK = _Search(_block_relink, abi.RELINK_DTYPES, _lib.relink_host, _lib.relink_device, ("path_best_state",), True)
 
 
 def relink_host(N, states, guides, seeds, max_steps=0, min_dist=1, local_search="pairs", walk=0, hist=False, figures=True):
     """mcq_relink_host: path relinking in the library's plain host code, NumPy in and out, no GPU.  Same result as relink_states."""
     s, g = _host_states(N, states), _host_states(N, guides)
-    n = s.shape[0]
     if g.shape != s.shape:
         raise ValueError(f"guides must have the shape of states, {s.shape}, got {g.shape}")
-    sd = _hop_seeds(seeds, n)
-    q = _block_relink(N, n, max_steps, min_dist, local_search, walk)
-    width = _relink_width(N, max_steps)
-    out = _host_outputs(q, s, abi.RELINK_DTYPES, {"energy_hist": (n, width)}, _relink_skip(hist, figures), like=("path_best_state",) if figures else ())
-    q.seeds, q.guide_in, q.hist_stride = sd.ctypes.data, g.ctypes.data, width
-    _lib.relink_host(q)
-    return out
+    n, width = s.shape[0], _relink_width(N, max_steps)
+    return _host_call(_RELINK, (N,), s, (max_steps, min_dist, local_search, walk), {"energy_hist": (n, width)} if hist else {}, seeds, width,
+                      lambda: {"guide_in": g}, figures)
 
 
 def relink_device(N, states, guides, seeds, max_steps=0, min_dist=1, local_search="pairs", walk=0, hist=False, figures=True, out=None, stream=None):
@@ -538,33 +520,11 @@ def relink_device(N, states, guides, seeds, max_steps=0, min_dist=1, local_searc
     out: `state` alone."""
     import torch
 
-    n = _device_states("relink_device", N, states)
-    dev = states.device
-    if not (isinstance(guides, torch.Tensor) and guides.device == dev and guides.dtype == torch.uint8 and guides.is_contiguous() and guides.shape == states.shape):
+    n, width = _device_states("relink_device", N, states), _relink_width(N, max_steps)
+    if not (isinstance(guides, torch.Tensor) and guides.device == states.device and guides.dtype == torch.uint8 and guides.is_contiguous() and guides.shape == states.shape):
         raise ValueError("relink_device takes guides as a contiguous uint8 tensor of the shape and device of states")
-    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
-            and tuple(seeds.shape) == (n,)):
-        raise ValueError(f"relink_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block_relink(N, n, max_steps, min_dist, local_search, walk)
-        width = _relink_width(N, max_steps)
-        res = {"state": _device_out(out, states)}
-        if figures:
-            res["path_best_state"] = torch.empty_like(states)
-            q.path_best_state = res["path_best_state"].data_ptr()
-        for k, dt in abi.RELINK_DTYPES.items():
-            if k == "energy_hist":
-                if hist:
-                    res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
-            elif figures:
-                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
-        q.seeds, q.state_in, q.guide_in, q.state_out, q.hist_stride = seeds.data_ptr(), states.data_ptr(), guides.data_ptr(), res["state"].data_ptr(), width
-        for k in abi.RELINK_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
-        _lib.relink_device(q, st)
-    return res
+    return _device_call(_RELINK, "relink_device", (N,), n, states, (max_steps, min_dist, local_search, walk), {"energy_hist": (n, width)} if hist else {},
+                        seeds, width, lambda: {"guide_in": guides}, figures, out=out, stream=stream)
 
 
 def relink_states(N, states, guides, seeds, max_steps=0, min_dist=1, local_search="pairs", walk=0, hist=False, figures=True):
@@ -577,19 +537,13 @@ def relink_states(N, states, guides, seeds, max_steps=0, min_dist=1, local_searc
     two aligned columns -- to `state`.  Returns a dict of NumPy arrays with the fields of FIELDS_RELINK (`energy_hist` only with
     hist=True: the energies along the walk, whose largest is `path_max_energy`, the barrier when less `energy_in`).  ValueError for what
     the library refuses (N outside 2 .. 32, no chain, max_steps or min_dist outside 0 .. N^2, a negative walk)."""
-    import torch
-
     s, g = _host_states(N, states), _host_states(N, guides)
     if g.shape != s.shape:
         raise ValueError(f"guides must have the shape of states, {s.shape}, got {g.shape}")
     sd = _hop_seeds(seeds, s.shape[0])
-    if s.shape[0] == 0:
-        _lib.relink_host(_block_relink(N, 0, max_steps, min_dist, local_search, walk))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res = relink_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(g).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), max_steps=max_steps,
-                        min_dist=min_dist, local_search=local_search, walk=walk, hist=hist, figures=figures)
-    torch.cuda.current_stream(dev).synchronize()
-    return to_numpy(res)
+    return _round_trip(_RELINK, (N,), (max_steps, min_dist, local_search, walk), s, lambda: (g, sd.view(np.int32)),
+                       lambda t, tg, ts: relink_device(N, t, tg, ts, max_steps=max_steps, min_dist=min_dist, local_search=local_search, walk=walk, hist=hist,
+                                                       figures=figures))
 
 
 N_IMAGES = 16  # the symmetries of the square times the flip of the heights
@@ -775,6 +729,9 @@ def _block3d(N, Q, n, max_passes):
     return q
 
 
+_QUENCH3D = _Search(_block3d, abi.QUENCH3D_DTYPES, _lib.quench3d_host, _lib.quench3d_device, (), False)
+
+
 def _queens_of(N, Q):
     return int(N) * int(N) if Q is None or int(Q) == 0 else int(Q)
 
@@ -795,12 +752,8 @@ def _host_queens(N, states, Q):
 
 def quench_queens_host(N, states, Q=None, max_passes=0, conflicts=True):
     """mcq_quench3d_host: the full_3d rule in the library's plain host code, NumPy in and out, no GPU.  Same result as quench_queens."""
-    s = _host_queens(N, states, Q)
-    n = s.shape[0]
-    q = _block3d(N, _queens_of(N, Q), n, max_passes)
-    out = _host_outputs(q, s, abi.QUENCH3D_DTYPES, {"conflicts": (n, s.shape[1] // 3)}, () if conflicts else ("conflicts",))
-    _lib.quench3d_host(q)
-    return out
+    s, Qn = _host_queens(N, states, Q), _queens_of(N, Q)
+    return _host_call(_QUENCH3D, (N, Qn), s, (max_passes,), {"conflicts": (s.shape[0], s.shape[1] // 3)} if conflicts else {})
 
 
 def quench_queens_device(N, states, Q=None, max_passes=0, out=None, conflicts=True, stream=None):
@@ -810,16 +763,8 @@ def quench_queens_device(N, states, Q=None, max_passes=0, out=None, conflicts=Tr
     placements go to; it may be `states` itself (in place), default a new one.  Returns a dict of tensors: `state` uint8 like `states`,
     `energy_in` (the recount of the input), `energy_out`, `n_moves`, `n_passes`, `flags` int32[n_chains] and, unless conflicts=False,
     `conflicts` int16[n_chains][Q] (the uint16 counts a(q, pos(q)) of the output; below 2^15, so the sign bit is never set)."""
-    import torch
-
     n, Qn = _device_queens("quench_queens_device", N, states, Q)
-    dev = states.device
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block3d(N, Qn, n, max_passes)
-        res = _device_outputs(q, states, out, abi.QUENCH3D_DTYPES, (n, Qn) if conflicts else None)
-        _lib.quench3d_device(q, st)
-    return res
+    return _device_call(_QUENCH3D, "quench_queens_device", (N, Qn), n, states, (max_passes,), {"conflicts": (n, Qn)} if conflicts else {}, out=out, stream=stream)
 
 
 def quench_queens(N, states, Q=None, max_passes=0, conflicts=True):
@@ -831,15 +776,8 @@ def quench_queens(N, states, Q=None, max_passes=0, conflicts=True):
     n_moves == 0 and n_passes == 1 was a local minimum already; flags bit 0 (abi.QUENCH3D_REPEATED) marks an input with two queens in
     one cell, which is recounted and handed back unmoved.  ValueError for what the library refuses (N outside 2 .. 32, Q outside
     2 .. N^3 - 1, no chain, a negative max_passes)."""
-    import torch
-
-    s = _host_queens(N, states, Q)
-    if s.shape[0] == 0:
-        _lib.quench3d_host(_block3d(N, _queens_of(N, Q), 0, max_passes))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res = quench_queens_device(N, torch.from_numpy(s).to(dev), Q=Q, max_passes=max_passes, conflicts=conflicts)
-    torch.cuda.current_stream(dev).synchronize()
-    return to_numpy(res)
+    return _round_trip(_QUENCH3D, (N, _queens_of(N, Q)), (max_passes,), _host_queens(N, states, Q), lambda: (),
+                       lambda t: quench_queens_device(N, t, Q=Q, max_passes=max_passes, conflicts=conflicts))
 
 
 FIELDS_HOP3D = ("state", "energy_in", "energy_start", "energy_out", "best_energy", "best_hop", "best_state", "n_accepted", "n_improved", "n_moves",
@@ -853,18 +791,15 @@ def _block_hop3d(N, Q, n, n_hops, kick, slack, first_hop):
     return q
 
 
+_HOP3D = _Search(_block_hop3d, abi.HOP3D_DTYPES, _lib.hop3d_host, _lib.hop3d_device, ("best_state",), True)
+
+
 def hop_queens_host(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, hist=False):
     """mcq_hop3d_host: basin hopping of full_3d placements in the library's plain host code, NumPy in and out, no GPU.  Same result as
     hop_queens, and it runs every shape (the kernel stops where a chain no longer fits the LDS: abi.hop3d_lds_bytes)."""
     s = _host_queens(N, states, Q)
-    n = s.shape[0]
-    sd = _hop_seeds(seeds, n)
-    q = _block_hop3d(N, _queens_of(N, Q), n, n_hops, kick, slack, first_hop)
-    width = max(int(n_hops), 0) + 1
-    out = _host_outputs(q, s, abi.HOP3D_DTYPES, {"energy_hist": (n, width)}, () if hist else ("energy_hist",), like=("best_state",))
-    q.seeds, q.hist_stride = sd.ctypes.data, width
-    _lib.hop3d_host(q)
-    return out
+    n, width = s.shape[0], max(int(n_hops), 0) + 1
+    return _host_call(_HOP3D, (N, _queens_of(N, Q)), s, (n_hops, kick, slack, first_hop), {"energy_hist": (n, width)} if hist else {}, seeds, width)
 
 
 def hop_queens_device(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, hist=False, out=None, stream=None):
@@ -875,29 +810,9 @@ def hop_queens_device(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_h
     default a new one.  Returns a dict of tensors with the fields of FIELDS_HOP3D: `state` and `best_state` uint8 like `states`;
     `energy_in`, `energy_start`, `energy_out`, `best_energy`, `flags` int32[n_chains]; `best_hop`, `n_accepted`, `n_improved`, `n_moves`,
     `n_passes`, `n_kicked` int64[n_chains]; and with hist=True `energy_hist` int32[n_chains][n_hops + 1]."""
-    import torch
-
-    n, Qn = _device_queens("hop_queens_device", N, states, Q)
-    dev = states.device
-    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
-            and tuple(seeds.shape) == (n,)):
-        raise ValueError(f"hop_queens_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block_hop3d(N, Qn, n, n_hops, kick, slack, first_hop)
-        width = max(int(n_hops), 0) + 1
-        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
-        for k, dt in abi.HOP3D_DTYPES.items():
-            if k != "energy_hist":
-                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
-            elif hist:
-                res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
-        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
-        for k in abi.HOP3D_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
-        _lib.hop3d_device(q, st)
-    return res
+    (n, Qn), width = _device_queens("hop_queens_device", N, states, Q), max(int(n_hops), 0) + 1
+    return _device_call(_HOP3D, "hop_queens_device", (N, Qn), n, states, (n_hops, kick, slack, first_hop), {"energy_hist": (n, width)} if hist else {},
+                        seeds, width, out=out, stream=stream)
 
 
 def hop_queens(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, hist=False):
@@ -911,19 +826,10 @@ def hop_queens(N, states, seeds, n_hops, Q=None, kick=2, slack=0, first_hop=0, h
     figures of the pieces combine as hop_states says, n_passes in the place of n_pair_moves.  ValueError for what the library refuses
     (N outside 2 .. 32, Q outside 2 .. N^3 - 1, no chain, kick outside 1 .. 1024, a negative n_hops, first_hop or slack, a chain above
     the LDS of a workgroup: N = 32 runs up to Q = 23 520)."""
-    import torch
-
     s = _host_queens(N, states, Q)
     sd = _hop_seeds(seeds, s.shape[0])
-    if s.shape[0] == 0:
-        _lib.hop3d_host(_block_hop3d(N, _queens_of(N, Q), 0, n_hops, kick, slack, first_hop))  # raises the library's refusal
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res = hop_queens_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_hops, Q=Q, kick=kick, slack=slack,
-                            first_hop=first_hop, hist=hist)
-    torch.cuda.current_stream(dev).synchronize()
-    out = to_numpy(res)
-    out["state"], out["best_state"] = out["state"].reshape(s.shape), out["best_state"].reshape(s.shape)
-    return out
+    return _round_trip(_HOP3D, (N, _queens_of(N, Q)), (n_hops, kick, slack, first_hop), s, lambda: (sd.view(np.int32),),
+                       lambda t, ts: hop_queens_device(N, t, ts, n_hops, Q=Q, kick=kick, slack=slack, first_hop=first_hop, hist=hist))
 
 
 FIELDS_TABU3D = FIELDS_TABU + ("flags",)
@@ -936,30 +842,17 @@ def _block_tabu3d(N, Q, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter
     return q
 
 
+_TABU3D = _Search(_block_tabu3d, abi.TABU3D_DTYPES, _lib.tabu3d_host, _lib.tabu3d_device, ("best_state",), True)
+
+
 def tabu_queens_host(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None,
                      hist=False, tabu_out=False):
     """mcq_tabu3d_host: tabu search of full_3d placements in the library's plain host code, NumPy in and out, no GPU.  Same result as
     tabu_queens, and it runs every shape (the kernel stops where a chain no longer fits the LDS: abi.tabu3d_lds_bytes)."""
     s = _host_queens(N, states, Q)
-    n = s.shape[0]
-    sd = _hop_seeds(seeds, n)
-    q = _block_tabu3d(N, _queens_of(N, Q), n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
-    width, cube = max(int(n_iters), 0) + 1, max(int(N), 0) ** 3
-    out = _host_outputs(q, s, abi.TABU3D_DTYPES, {"energy_hist": (n, width), "tabu_out": (n, cube)}, _tabu_skip(hist, tabu_out), like=("best_state",))
-    q.seeds, q.hist_stride = sd.ctypes.data, width
-    keep = []
-    if tabu_in is not None:
-        keep.append(np.ascontiguousarray(tabu_in, dtype=np.uint16).reshape(-1))
-        if keep[-1].shape[0] != n * cube:
-            raise ValueError(f"tabu_in must be uint16[n_chains = {n}][N^3 = {cube}], got {np.shape(tabu_in)}")
-        q.tabu_in = keep[-1].ctypes.data
-    if best_floor is not None:
-        keep.append(np.ascontiguousarray(best_floor, dtype=np.int32).reshape(-1))
-        if keep[-1].shape[0] != n:
-            raise ValueError(f"best_floor must be int32[n_chains = {n}], got {np.shape(best_floor)}")
-        q.best_floor = keep[-1].ctypes.data
-    _lib.tabu3d_host(q)
-    return out
+    n, width, cube = s.shape[0], max(int(n_iters), 0) + 1, max(int(N), 0) ** 3
+    return _host_call(_TABU3D, (N, _queens_of(N, Q)), s, (n_iters, tenure, tenure_rand, tenure_conf, first_iter), _tabu_shapes(n, width, cube, hist, tabu_out),
+                      seeds, width, lambda: _tabu_host_inputs(n, cube, tabu_in, best_floor))
 
 
 def tabu_queens_device(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None,
@@ -973,44 +866,10 @@ def tabu_queens_device(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand
     `states`; `energy_in`, `energy_out`, `best_energy`, `flags` int32[n_chains]; `best_iter`, `n_moves`, `n_aspired`, `n_uphill`,
     `n_stalled` int64[n_chains]; with hist=True `energy_hist` int32[n_chains][n_iters + 1]; with tabu_out=True `tabu_out`
     int16[n_chains][N^3] (the uint16 stamps; tabu_to_numpy views them so)."""
-    import torch
-
-    n, Qn = _device_queens("tabu_queens_device", N, states, Q)
-    dev = states.device
-    if not (isinstance(seeds, torch.Tensor) and seeds.device == dev and seeds.dtype in (torch.int32, getattr(torch, "uint32", torch.int32)) and seeds.is_contiguous()
-            and tuple(seeds.shape) == (n,)):
-        raise ValueError(f"tabu_queens_device takes seeds as a contiguous int32 or uint32 tensor [n_chains = {n}] on the device of states")
-    cube = max(int(N), 0) ** 3
-    if tabu_in is not None and not (isinstance(tabu_in, torch.Tensor) and tabu_in.device == dev and tabu_in.is_contiguous() and tabu_in.numel() == n * cube
-                                    and tabu_in.dtype in (torch.int16, getattr(torch, "uint16", torch.int16))):
-        raise ValueError(f"tabu_queens_device takes tabu_in as a contiguous int16 or uint16 tensor [n_chains = {n}][N^3 = {cube}] on the device of states")
-    if best_floor is not None and not (isinstance(best_floor, torch.Tensor) and best_floor.device == dev and best_floor.is_contiguous()
-                                       and best_floor.dtype == torch.int32 and tuple(best_floor.shape) == (n,)):
-        raise ValueError(f"tabu_queens_device takes best_floor as a contiguous int32 tensor [n_chains = {n}] on the device of states")
-    st = torch.cuda.current_stream(dev) if stream is None else stream
-    with torch.cuda.device(dev), torch.cuda.stream(st):
-        q = _block_tabu3d(N, Qn, n, n_iters, tenure, tenure_rand, tenure_conf, first_iter)
-        width = max(int(n_iters), 0) + 1
-        res = {"state": _device_out(out, states), "best_state": torch.empty_like(states)}
-        for k, dt in abi.TABU3D_DTYPES.items():
-            if k == "energy_hist":
-                if hist:
-                    res[k] = torch.empty((n, width), dtype=torch.int32, device=dev)
-            elif k == "tabu_out":
-                if tabu_out:
-                    res[k] = torch.empty((n, cube), dtype=torch.int16, device=dev)
-            else:
-                res[k] = torch.empty(n, dtype=torch.int64 if dt is np.int64 else torch.int32, device=dev)
-        q.seeds, q.state_in, q.state_out, q.best_state, q.hist_stride = seeds.data_ptr(), states.data_ptr(), res["state"].data_ptr(), res["best_state"].data_ptr(), width
-        if tabu_in is not None:
-            q.tabu_in = tabu_in.data_ptr()
-        if best_floor is not None:
-            q.best_floor = best_floor.data_ptr()
-        for k in abi.TABU3D_DTYPES:
-            if k in res:
-                setattr(q, k, res[k].data_ptr())
-        _lib.tabu3d_device(q, st)
-    return res
+    (n, Qn), width, cube = _device_queens("tabu_queens_device", N, states, Q), max(int(n_iters), 0) + 1, max(int(N), 0) ** 3
+    return _device_call(_TABU3D, "tabu_queens_device", (N, Qn), n, states, (n_iters, tenure, tenure_rand, tenure_conf, first_iter),
+                        _tabu_shapes(n, width, cube, hist, tabu_out), seeds, width,
+                        lambda: _tabu_device_inputs("tabu_queens_device", n, cube, states.device, tabu_in, best_floor), out=out, stream=stream)
 
 
 def tabu_queens(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, tenure_conf=0, first_iter=0, tabu_in=None, best_floor=None,
@@ -1027,23 +886,14 @@ def tabu_queens(N, states, seeds, n_iters, Q=None, tenure=10, tenure_rand=0, ten
     N = 32 runs up to Q = 14 272 on the device) is run by tabu_queens_host, which gives the same result.  ValueError for what the
     library refuses (N outside 2 .. 32, Q outside 2 .. N^3 - 1, no chain, tenure outside 0 .. 8192, tenure_rand outside 0 .. 4095,
     tenure_conf outside 0 .. 64, a negative n_iters or first_iter)."""
-    import torch
-
     s = _host_queens(N, states, Q)
     sd = _hop_seeds(seeds, s.shape[0])
     kw = dict(Q=Q, tenure=tenure, tenure_rand=tenure_rand, tenure_conf=tenure_conf, first_iter=first_iter, hist=hist, tabu_out=tabu_out)
-    if s.shape[0] == 0:
-        _lib.tabu3d_host(_block_tabu3d(N, _queens_of(N, Q), 0, n_iters, tenure, tenure_rand, tenure_conf, first_iter))  # raises the library's refusal
-    if abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and abi.tabu3d_lds_bytes(N, Q) > abi.MAX_TABU3D_LDS:
+    # (no chain is refused by _round_trip, as before the fallback: the host wrapper would look at tabu_in first)
+    if s.shape[0] and abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and abi.tabu3d_lds_bytes(N, Q) > abi.MAX_TABU3D_LDS:
         return tabu_queens_host(N, s, sd, n_iters, tabu_in=tabu_in, best_floor=best_floor, **kw)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    ti = None if tabu_in is None else torch.from_numpy(np.ascontiguousarray(tabu_in, dtype=np.uint16).view(np.int16)).to(dev)
-    bf = None if best_floor is None else torch.from_numpy(np.ascontiguousarray(best_floor, dtype=np.int32)).to(dev)
-    res = tabu_queens_device(N, torch.from_numpy(s).to(dev), torch.from_numpy(sd.view(np.int32)).to(dev), n_iters, tabu_in=ti, best_floor=bf, **kw)
-    torch.cuda.current_stream(dev).synchronize()
-    out = tabu_to_numpy(res)
-    out["state"], out["best_state"] = out["state"].reshape(s.shape), out["best_state"].reshape(s.shape)
-    return out
+    return _round_trip(_TABU3D, (N, _queens_of(N, Q)), (n_iters, tenure, tenure_rand, tenure_conf, first_iter), s, lambda: _tabu_arrays(sd, tabu_in, best_floor),
+                       lambda t, ts, ti, bf: tabu_queens_device(N, t, ts, n_iters, tabu_in=ti, best_floor=bf, **kw))
 
 
 def check_tabu_queens(tabu_iters, tabu_tenure, tabu_tenure_rand, hops, N, Q, board):
