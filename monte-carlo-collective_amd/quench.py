@@ -37,6 +37,12 @@ hops is one launch.  queens_of_boards carries board placements into the cube.  O
 tabu_queens, tabu_queens_device and tabu_queens_host walk on from a full_3d placement (include/mcq.h: mcq_tabu3d; csrc/mcq_tabu3d.hip):
 the best admissible move of a conflicting queen to a free cell in every iteration, also when it raises the energy, with the cell left
 forbidden for a while.  A whole run is one launch.  Opt-in like everything here.
+
+relink_queens, relink_queens_device and relink_queens_host combine two full_3d placements (include/mcq.h: mcq_relink3d;
+csrc/mcq_relink3d.hip): a walk towards the guide's set of cells, one queen at a time and always the cheapest remaining (queen, cell)
+pair, with the best placement met on the way handed to the single-queen descent.  queens_images and nearest_queens_image bring a guide
+into the one of its 48 images under the cube's symmetries that is closest to the placement, and relink_queens_pool runs rounds of
+relinking over a pool.  A whole call is one launch.  Opt-in like everything here.
 """
 import collections
 
@@ -926,3 +932,252 @@ def queens_of_boards(N, boards):
     c = np.arange(N * N)
     out[:, :, 0], out[:, :, 1], out[:, :, 2] = (c // N).astype(np.uint8), (c % N).astype(np.uint8), h
     return out.reshape(h.shape[0], 3 * N * N)
+
+
+FIELDS_RELINK3D = ("state", "path_best_state", "distance_in", "n_steps", "path_best_step", "energy_in", "path_best_energy", "path_max_energy",
+                   "energy_out", "n_moves", "n_passes", "energy_hist", "flags")
+
+
+def _block_relink3d(N, Q, n, max_steps, min_dist, walk):
+    q = abi.Relink3d()
+    q.N, q.n_queens, q.n_chains, q.walk = int(N), int(Q), int(n), int(walk)
+    q.max_steps, q.min_dist = int(max_steps), int(min_dist)
+    return q
+
+
+def _relink3d_width(N, Q, max_steps):
+    """W + 1 of the rule, item 5: the entries of a chain's history."""
+    return (int(max_steps) if int(max_steps) > 0 else max(_queens_of(N, Q), 0)) + 1
+
+
+_RELINK3D = _Search(_block_relink3d, abi.RELINK3D_DTYPES, _lib.relink3d_host, _lib.relink3d_device, ("path_best_state",), True)
+
+
+def relink_queens_host(N, states, guides, seeds, Q=None, max_steps=0, min_dist=1, walk=0, hist=False, figures=True):
+    """mcq_relink3d_host: path relinking of full_3d placements in the library's plain host code, NumPy in and out, no GPU.  Same result
+    as relink_queens, and it runs every shape (the kernel stops where a chain no longer fits the LDS: abi.relink3d_lds_bytes)."""
+    s, g = _host_queens(N, states, Q), _host_queens(N, guides, Q)
+    if g.shape != s.shape:
+        raise ValueError(f"guides must have the shape of states, {s.shape}, got {g.shape}")
+    n, width = s.shape[0], _relink3d_width(N, Q, max_steps)
+    return _host_call(_RELINK3D, (N, _queens_of(N, Q)), s, (max_steps, min_dist, walk), {"energy_hist": (n, width)} if hist else {}, seeds, width,
+                      lambda: {"guide_in": g}, figures)
+
+
+def relink_queens_device(N, states, guides, seeds, Q=None, max_steps=0, min_dist=1, walk=0, hist=False, figures=True, out=None, stream=None):
+    """mcq_relink3d_device on two torch uint8 tensors [n_chains][3 Q] or [n_chains][Q][3] of the current device, the placements and
+    their guides (Q=None means N^2), and an int32 or uint32 tensor `seeds` [n_chains] on the same device, enqueued on `stream` (default:
+    torch's current stream).  ONE kernel whatever the distances are.  Asynchronous: nothing is copied back and nothing synchronises.
+    `out` (optional) is the tensor the final placements go to; it may be `states` itself (in place) and may not be `guides`; default a
+    new one.  Returns a dict of tensors with the fields of FIELDS_RELINK3D: `state` and `path_best_state` uint8 like `states`;
+    `distance_in`, `n_steps`, `path_best_step`, `energy_in`, `path_best_energy`, `path_max_energy`, `energy_out`, `flags`
+    int32[n_chains]; `n_moves`, `n_passes` int64[n_chains]; with hist=True `energy_hist` int32[n_chains][W + 1], W = max_steps or Q.
+    figures=False leaves every optional output but the history out: `state` alone."""
+    import torch
+
+    (n, Qn), width = _device_queens("relink_queens_device", N, states, Q), _relink3d_width(N, Q, max_steps)
+    if not (isinstance(guides, torch.Tensor) and guides.device == states.device and guides.dtype == torch.uint8 and guides.is_contiguous() and guides.shape == states.shape):
+        raise ValueError("relink_queens_device takes guides as a contiguous uint8 tensor of the shape and device of states")
+    return _device_call(_RELINK3D, "relink_queens_device", (N, Qn), n, states, (max_steps, min_dist, walk), {"energy_hist": (n, width)} if hist else {},
+                        seeds, width, lambda: {"guide_in": guides}, figures, out=out, stream=stream)
+
+
+def relink_queens(N, states, guides, seeds, Q=None, max_steps=0, min_dist=1, walk=0, hist=False, figures=True):
+    """Path relinking of full_3d placements on the GPU: `states` and `guides` are uint8[n_chains][3 Q] or [n_chains][Q][3] (Q triples
+    (i, j, k); Q=None means N^2), bytes >= N are clamped to N - 1; `seeds` is uint32[n_chains].  A guide is read as a SET of cells: the
+    order of its queens means nothing.  Each placement walks towards its guide: a step moves one of the queens that stand on no cell of
+    the guide to one of the guide's cells that hold no queen, the (queen, cell) pair whose change of energy is smallest -- a rise too;
+    ties by a random rotation of the queens and of the cells that `walk` and the seed decide --, for max_steps steps or, with 0, all the
+    way.  Of the placements on the way that are at least max(1, min_dist) moves from the start and min_dist from the guide, the one with
+    the smallest energy (`path_best_state`, the start when there is none) then descends under single-queen moves (quench_queens with
+    max_passes = 0) to `state`; queens keep the indices they have in `states`.  Returns a dict of NumPy arrays with the fields of
+    FIELDS_RELINK3D (`energy_hist` only with hist=True); flags bit 0 (abi.RELINK3D_REPEATED) marks a placement and bit 1
+    (abi.RELINK3D_GUIDE_REPEATED) a guide with two queens in one cell: the chain is recounted and handed back unmoved.  A shape whose
+    chain is above the LDS of a workgroup (abi.relink3d_lds_bytes(N, Q) > abi.MAX_RELINK3D_LDS: N = 32 runs up to Q = 11 248 on the
+    device) is run by relink_queens_host, which gives the same result.  ValueError for what the library refuses (N outside 2 .. 32, Q
+    outside 2 .. N^3 - 1, no chain, max_steps or min_dist outside 0 .. Q, a negative walk)."""
+    s, g = _host_queens(N, states, Q), _host_queens(N, guides, Q)
+    if g.shape != s.shape:
+        raise ValueError(f"guides must have the shape of states, {s.shape}, got {g.shape}")
+    sd = _hop_seeds(seeds, s.shape[0])
+    kw = dict(Q=Q, max_steps=max_steps, min_dist=min_dist, walk=walk, hist=hist, figures=figures)
+    if s.shape[0] and abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D and abi.relink3d_lds_bytes(N, Q) > abi.MAX_RELINK3D_LDS:
+        return relink_queens_host(N, s, g, sd, **kw)
+    return _round_trip(_RELINK3D, (N, _queens_of(N, Q)), (max_steps, min_dist, walk), s, lambda: (g, sd.view(np.int32)),
+                       lambda t, tg, ts: relink_queens_device(N, t, tg, ts, **kw))
+
+
+N_QUEENS_IMAGES = 48  # the symmetries of the cube: the 6 orders of the axes times the 8 mirrorings
+_AXES = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
+
+
+def _queens_image(N, t, s):
+    """Image s of the triples t, [n][Q][3] (NumPy or torch), without checks."""
+    perm, flips = _AXES[s >> 3], ((s >> 2) & 1, (s >> 1) & 1, s & 1)
+    cols = [(N - 1) - t[..., perm[a]] if flips[a] else t[..., perm[a]] for a in range(3)]
+    if isinstance(t, np.ndarray):
+        return np.stack(cols, axis=-1)
+    import torch
+
+    return torch.stack(cols, dim=-1)
+
+
+def _queens_triples(fn, N, states, Q):
+    """The triples [n][Q][3] of queens_images / nearest_queens_image, NumPy or torch, with their checks."""
+    N, Qn = int(N), _queens_of(N, Q)
+    if not abi.MIN_N <= N <= abi.MAX_N_QUENCH3D:
+        raise ValueError(f"N out of range [{abi.MIN_N}, {abi.MAX_N_QUENCH3D}]: {N}")
+    if isinstance(states, np.ndarray) or not hasattr(states, "is_cuda"):
+        t = _host_queens(N, states, Q)
+    else:
+        import torch
+
+        ok = (states.dim() == 2 and int(states.shape[1]) == 3 * Qn) or (states.dim() == 3 and tuple(states.shape[1:]) == (Qn, 3))
+        if states.dtype != torch.uint8 or not ok:
+            raise ValueError(f"states must be uint8[n][{3 * Qn}] or [n][{Qn}][3] (final_state layout of full_3d), got {tuple(states.shape)}")
+        t = states
+    t = t.reshape(t.shape[0], Qn, 3)
+    if t.shape[0] and Qn and int(t.max()) >= N:
+        raise ValueError(f"{fn}: an entry of states is >= N = {N}")
+    return t
+
+
+def queens_images(N, states, Q=None):
+    """The 48 images of full_3d placements under the symmetries of the cube, as [48][n][3 Q]: `states` is uint8[n][3 Q] or [n][Q][3], a
+    NumPy array or a torch tensor (the result is of the same kind, on the same device; Q=None means N^2).  Image s = 8 p + 4 f0 + 2 f1 +
+    f2 of a queen x = (x0, x1, x2): first the axes are reordered, y_a = x_{P[p][a]} with P = ((0, 1, 2), (0, 2, 1), (1, 0, 2),
+    (1, 2, 0), (2, 0, 1), (2, 1, 0)) (itertools.permutations order); then, where f_a = 1, y_a becomes N - 1 - y_a.  Image 0 is the
+    placement itself; queens keep their indices.  All 48 have the energy of the placement: a reordering of the axes and a mirroring
+    keep |di|, |dj|, |dk| as a set, which is all the attack rule reads.  ValueError for an entry >= N (a byte that the rule would clamp
+    has no mirror image)."""
+    t = _queens_triples("queens_images", N, states, Q)
+    imgs = [_queens_image(int(N), t, s).reshape(t.shape[0], -1) for s in range(N_QUEENS_IMAGES)]
+    if isinstance(t, np.ndarray):
+        return np.stack(imgs)
+    import torch
+
+    return torch.stack(imgs)
+
+
+def _cell_sets(N, t):
+    """The cells of the triples t, [n][Q][3], as a bitmap bool[n][N^3] (NumPy or torch)."""
+    n, C = t.shape[0], N ** 3
+    if isinstance(t, np.ndarray):
+        cell = (t[..., 0].astype(np.int64) * N + t[..., 1]) * N + t[..., 2]
+        occ = np.zeros((n, C), dtype=bool)
+        occ[np.arange(n)[:, None], cell] = True
+        return occ
+    import torch
+
+    cell = (t[..., 0].to(torch.int64) * N + t[..., 1]) * N + t[..., 2]
+    return torch.zeros((n, C), dtype=torch.bool, device=t.device).scatter_(1, cell, True)
+
+
+def _nearest_queens(N, ts, tg):
+    """(image, index, distance) of nearest_queens_image from checked triples [n][Q][3] of one kind."""
+    occ = _cell_sets(N, ts)
+    best = None
+    for s in range(N_QUEENS_IMAGES):  # ascending, and replaced only when strictly nearer: the smallest index on ties
+        img = _queens_image(N, tg, s)
+        dist = (occ & ~_cell_sets(N, img)).sum(1)
+        if best is None:
+            best = [img, dist * 0 + s, dist]
+            continue
+        nearer = dist < best[2]
+        if isinstance(ts, np.ndarray):
+            best = [np.where(nearer[:, None, None], img, best[0]), np.where(nearer, s, best[1]), np.where(nearer, dist, best[2])]
+        else:
+            import torch
+
+            best = [torch.where(nearer[:, None, None], img, best[0]), torch.where(nearer, s, best[1]), torch.where(nearer, dist, best[2])]
+    img = best[0].reshape(ts.shape[0], -1)
+    if isinstance(ts, np.ndarray):
+        return np.ascontiguousarray(img), best[1].astype(np.int32), best[2].astype(np.int32)
+    import torch
+
+    return img.contiguous(), best[1].to(torch.int32), best[2].to(torch.int32)
+
+
+def nearest_queens_image(N, states, guides, Q=None):
+    """Of the 48 images of each guide (queens_images) the one with the smallest set distance |cells(A) \\ cells(G')| to its placement A:
+    returns (the images uint8[n][3 Q], their indices int32[n] in queens_images' numbering, the distances int32[n]); the smallest index
+    on ties.  The distance is the d0 of relink_queens between the two, so an aligned walk is as short as the cube's symmetry allows,
+    and the guide's energy is the same.  NumPy arrays or torch tensors, both of the same kind; no kernel of the library runs.
+    ValueError for an entry >= N in either."""
+    tg = _queens_triples("nearest_queens_image", N, guides, Q)
+    if isinstance(tg, np.ndarray) != (isinstance(states, np.ndarray) or not hasattr(states, "is_cuda")):
+        raise ValueError("nearest_queens_image takes states and guides of the same kind, NumPy arrays or torch tensors")
+    ts = _queens_triples("nearest_queens_image", N, states, Q)
+    if tuple(ts.shape) != tuple(tg.shape) or (not isinstance(tg, np.ndarray) and ts.device != tg.device):
+        raise ValueError(f"states must have the shape and device of guides, {tuple(tg.shape)}, got {tuple(ts.shape)}")
+    return _nearest_queens(int(N), ts, tg)
+
+
+def _queens_pool_args(N, Q, n, rounds, min_dist, partner_seed):
+    """(min_dist, the shifts s_k of the rounds) of relink_queens_pool / relink_queens_pool_host, and their refusals."""
+    if int(rounds) < 1:
+        raise ValueError(f"rounds must be >= 1, got {rounds}")
+    if n < 2:
+        raise ValueError(f"relink_queens_pool needs a pool of at least 2 placements, got {n}")
+    md = max(1, _queens_of(N, Q) // 8) if min_dist is None else int(min_dist)
+    rs = np.random.RandomState(int(partner_seed))
+    return md, [int(rs.randint(1, n)) for _ in range(int(rounds))]
+
+
+def relink_queens_pool_host(N, states, seeds, rounds, Q=None, min_dist=None, align=True, partner_seed=0):
+    """relink_queens_pool in NumPy over relink_queens_host: the same pool, energies and counts, no GPU."""
+    s = _host_queens(N, states, Q)
+    n = s.shape[0]
+    md, shifts = _queens_pool_args(N, Q, n, rounds, min_dist, partner_seed)
+    if abi.MIN_N <= int(N) <= abi.MAX_N_QUENCH3D:
+        s = np.minimum(s, np.uint8(int(N) - 1))
+    sd = _hop_seeds(seeds, n)
+    pool, energy, n_replaced, best = s.copy(), None, [], []
+    for k, shift in enumerate(shifts):
+        guides = np.roll(pool, shift, axis=0)
+        if align:
+            guides = _nearest_queens(int(N), pool.reshape(n, -1, 3), guides.reshape(n, -1, 3))[0]
+        r = relink_queens_host(N, pool, guides, sd, Q=Q, min_dist=md, walk=k)
+        better = r["energy_out"] < r["energy_in"]
+        pool = np.where(better[:, None], r["state"], pool)
+        energy = np.where(better, r["energy_out"], r["energy_in"]).astype(np.int32)
+        n_replaced.append(int(better.sum()))
+        best.append(int(energy.min()))
+    return {"state": pool, "energy": energy, "n_replaced": np.array(n_replaced, dtype=np.int64), "best_energy": np.array(best, dtype=np.int32)}
+
+
+def relink_queens_pool(N, states, seeds, rounds, Q=None, min_dist=None, align=True, partner_seed=0, stream=None):
+    """Rounds of path relinking over a pool of full_3d placements on the GPU: `states` is a torch uint8 tensor [n][3 Q] on the device
+    (n >= 2; bytes >= N are clamped to N - 1 first; Q=None means N^2), `seeds` an int32 or uint32 tensor [n].  Round k = 0 .. rounds - 1
+    takes as the guide of slot r the placement of slot (r - s_k) mod n (torch.roll by s_k, drawn from 1 .. n - 1 with
+    np.random.RandomState(partner_seed), one draw per round), with align=True its image closest to the slot's placement
+    (nearest_queens_image), and calls relink_queens_device with walk = k and min_dist (default max(1, Q / 8)).  A slot takes the call's
+    `state` when its energy_out is strictly below the slot's own energy; otherwise it keeps its placement.  Everything stays on the
+    device, on `stream` (default: torch's current stream), with one synchronisation at the end.  Returns a dict: `state` uint8[n][3 Q]
+    and `energy` int32[n], tensors; `n_replaced` int64[rounds] and `best_energy` int32[rounds] (the pool's smallest energy behind each
+    round), NumPy arrays."""
+    import torch
+
+    n, Qn = _device_queens("relink_queens_pool", N, states, Q)
+    if states.dim() != 2:
+        raise ValueError(f"relink_queens_pool takes states as uint8[n][{3 * Qn}], got {tuple(states.shape)}")
+    md, shifts = _queens_pool_args(N, Q, n, rounds, min_dist, partner_seed)
+    N = int(N)
+    dev = states.device
+    st = torch.cuda.current_stream(dev) if stream is None else stream
+    with torch.cuda.device(dev), torch.cuda.stream(st):
+        pool = states.clamp(max=N - 1) if abi.MIN_N <= N <= abi.MAX_N_QUENCH3D else states
+        energy, n_replaced, best = None, [], []
+        for k, shift in enumerate(shifts):
+            guides = torch.roll(pool, shift, 0)
+            if align:
+                guides = _nearest_queens(N, pool.reshape(n, -1, 3), guides.reshape(n, -1, 3))[0]
+            r = relink_queens_device(N, pool, guides, seeds, Q=Q, min_dist=md, walk=k, stream=st)
+            better = r["energy_out"] < r["energy_in"]
+            pool = torch.where(better.unsqueeze(1), r["state"], pool)
+            energy = torch.where(better, r["energy_out"], r["energy_in"])
+            n_replaced.append(better.sum())
+            best.append(energy.min())
+        n_replaced, best = torch.stack(n_replaced), torch.stack(best)
+        st.synchronize()
+    return {"state": pool, "energy": energy, "n_replaced": n_replaced.cpu().numpy().astype(np.int64), "best_energy": best.cpu().numpy().astype(np.int32)}
