@@ -1463,6 +1463,106 @@ int mcq_relink3d_device(const mcq_relink3d* q, void* hip_stream);
  * to the kernel bit for bit on every output. */
 int mcq_relink3d_host(const mcq_relink3d* q);
 
+/*
+ * The n-fold way (Bortz, Kalos, Lebowitz): a rejection-free form of the Metropolis dynamics of board placements (csrc/mcq_nfold.hip)
+ * -- NOT a mode of the reference; never a default, like everything above that is labelled so.  The reference proposes one random
+ * column and one random height per step and rejects most of them; this block holds the acceptance weight of all N^2 (N - 1) moves of
+ * a board, draws the next ACCEPTED move in proportion to its weight and advances the clock by the time the Metropolis chain would
+ * have spent rejecting.  The process is the Metropolis chain with the same stationary distribution and the same time axis, counted
+ * in Metropolis steps.  Boards only, N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS.  The rule is integer-exact:
+ *   1. INPUT.  Every byte of state_in is clamped to N - 1; a(c, k) and E are those of the mcq_quench rule.  energy_in is the recount.
+ *   2. SEGMENTS.  A call runs n_segs segments of seg_steps Metropolis steps each, 1 <= seg_steps <= 2^31.  Segment s = 0 .. n_segs - 1
+ *      has the global index g = first_seg + s and the weight row T_s = table[s][0 .. table_len - 1], uint32, 1 <= table_len = D <=
+ *      MCQ_MAX_NFOLD_TABLE (a difference never exceeds 4 (N - 1) = 124); every entry is <= 2^24.  beta is constant inside a segment:
+ *      T_s[d] = floor(2^24 exp(-beta_s d)) is what the Python side builds, but the rows are the caller's.
+ *   3. WEIGHTS.  For a column c and a height k != h(c):  d = a(c, k) - a(c, h(c)),  w(c, k) = T_s[min(max(d, 0), D - 1)],
+ *      R(c) = sum over k of w(c, k) in uint32, W = sum over c of R(c) in uint64; W <= M 2^24 < 2^40 with M = N^2 (N - 1).
+ *      W / (M 2^24) is the probability that one Metropolis step of the reference is accepted.
+ *   4. TIME is counted in units of 2^-MCQ_NFOLD_TIME_BITS = 2^-12 step.  A chain holds `need`, a uint64: the hazard left until its
+ *      next event.  At the start of a segment left = seg_steps << 12.  Repeat, with tau = max(1, floor((need << 12) / W)):
+ *        if W > 0 and tau <= left:  left -= tau, the event fires (items 5 and 6) and need is drawn anew;
+ *        otherwise:  need -= floor(left W / 2^12) (the product fits 64 bits whenever this branch is taken; W = 0 leaves need as it
+ *        is), and the segment ends.
+ *      So a strict minimum under a row with T[d > 0] = 0 sleeps, and its need is kept.
+ *   5. DRAWS.  One Philox block per event: block e of chain r is
+ *        (x0, x1, x2, x3) = philox4x32-10(counter = (low 32 bits of e, high 32 bits of e, 0, 0), key = (seeds[r], 11))
+ *      (key words 0 - 10 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d, mcq_tabu,
+ *      mcq_tabu3d, mcq_relink and mcq_relink3d; 11 is this block's).  e is the chain's own event counter; it starts at events_in[r],
+ *      or at 0 when events_in is NULL.  x2 of block e gives the need of the wait that ENDS in event e:
+ *        need = M l(x2),   l(x) = z clock_ln2 + clock_table[y],
+ *      z = the number of leading zero bits of x (32 for x = 0) and y = bits 30 .. 23 of x << z: the 8 bits below the leading one
+ *      bit, zeros where x has none; y = 0 for x = 0.  clock_table is uint32[256] with every entry <= 2^26 and clock_ln2 <= 2^24, so
+ *      need < 2^45.  With clock_ln2 = round(2^24 ln 2) and clock_table[i] = round(-2^24 ln((256 + i + 1/2) / 512)), l / 2^24 is an
+ *      exponential variate of mean 1 to about 1e-6; clock_ln2 = 0 and a table of 2^24 give the deterministic expected waiting time.
+ *      A chain without need_in draws its first need from block events_in[r]; a need_in entry is < 2^45, like a drawn one.
+ *      x0 and x1 of block e choose the move of event e:  X = x0 2^32 + x1,  U = floor(X W / 2^64) from the full 128-bit product, and
+ *      the move is the first (c, k) in the order c ascending, k ascending, k != h(c), whose inclusive prefix sum of w exceeds U.
+ *      x3 is unused.
+ *   6. EVENT.  h(c) = k, E += d, e += 1; n_uphill counts the events with d > 0, n_flat those with d = 0.  The best values follow a
+ *      strictly lower E at every event: best_energy, best_state and
+ *        best_step = s seg_steps + (((seg_steps << 12) - left) >> 12),
+ *      relative to the call, `left` read behind the event's tau.  They start as energy_in, the clamped input and 0.
+ *      energy_hist[r][0 .. n_segs] (optional) holds the recount and then E at the end of every segment.
+ *   7. OUTPUTS.  state_out, best_state; energy_in, energy_out, best_energy; best_step, events_out (e behind the call), n_uphill,
+ *      n_flat; need_out; weight_out = W of the output under the call's last row (0 when n_segs = 0): the Metropolis acceptance rate
+ *      there times M 2^24.
+ *   8. CUTTING A RUN.  A run cut at a segment boundary is the unbroken run: the caller carries state_out -> state_in, need_out ->
+ *      need_in, events_out -> events_in and first_seg, and hands each piece its rows.  n_segs = 0 is a recount and a copy.
+ * Chains do not interact and a call reads all of a chain's inputs before it writes any of its outputs, so state_out may be state_in.
+ *
+ * mcq_nfold_device keeps a chain in the LDS of one wavefront: the table a(c, k) in the layout of csrc/mcq_table.h, the heights and
+ * the best placement (a byte per column each), R(c) (a dword per column, padded to an odd stride per lane) and the staged row T_s.
+ */
+#define MCQ_MAX_NFOLD_TABLE 128 /* the largest table_len of mcq_nfold: 4 (MCQ_MAX_N_QUENCH_PAIRS - 1) = 124 is the largest difference */
+#define MCQ_NFOLD_TIME_BITS 12  /* time is counted in units of 2^-12 Metropolis step */
+#define MCQ_NFOLD_WEIGHT_BITS 24 /* no entry of a weight row exceeds 2^24 */
+#define MCQ_NFOLD_CLOCK_BITS 26 /* no entry of clock_table exceeds 2^26; clock_ln2 <= 2^24 */
+#define MCQ_NFOLD_NEED_BITS 45  /* need < 2^45 */
+#define MCQ_NFOLD_STEP_BITS 50  /* (first_seg + n_segs) seg_steps < 2^50 */
+typedef struct mcq_nfold {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS */
+    int32_t mode;           /* MCQ_MODE_BOARD; anything else is MCQ_EINVAL */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_segs;         /* >= 0; 0 = a recount and a copy */
+    int64_t first_seg;      /* >= 0: the global index of the call's first segment */
+    int64_t seg_steps;      /* 1 .. 2^31 Metropolis steps per segment; (first_seg + n_segs) seg_steps < 2^50 */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint32_t* table;  /* [n_segs][table_len]: the weight rows, every entry <= 2^24; may be NULL when n_segs = 0 */
+    int64_t table_len;      /* D: 1 .. MCQ_MAX_NFOLD_TABLE */
+    const uint32_t* clock_table; /* [256]: every entry <= 2^26 */
+    int64_t clock_ln2;      /* 0 .. 2^24 */
+    const uint64_t* need_in; /* optional [n_chains]: the hazard left from the piece before, each < 2^45; NULL: drawn from block events_in[r] */
+    const int64_t* events_in; /* optional [n_chains]: the event counters the chains start at, each >= 0; NULL: 0 */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;     /* [n_chains][N*N]; may be state_in */
+    uint8_t* best_state;    /* optional [n_chains][N*N]; neither state_in nor state_out */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;    /* optional [n_chains] */
+    int32_t* best_energy;   /* optional [n_chains] */
+    int64_t* best_step;     /* optional [n_chains]: the Metropolis step of the call at which best_energy was first reached; 0 = the input */
+    int64_t* events_out;    /* optional [n_chains]: the event counter behind the call */
+    int64_t* n_uphill;      /* optional [n_chains]: events of this call with d > 0 */
+    int64_t* n_flat;        /* optional [n_chains]: events of this call with d = 0 */
+    uint64_t* need_out;     /* optional [n_chains] */
+    uint64_t* weight_out;   /* optional [n_chains]: W of the output under the last row; 0 when n_segs = 0 */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_segs */
+    int64_t hist_stride;    /* >= n_segs + 1 when energy_hist is given; not read otherwise */
+} mcq_nfold;
+
+/* the message of the last error of the calling thread from the two mcq_nfold_* calls below (they do not set mcq_last_error()) */
+const char* mcq_nfold_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_segs is; asynchronous: nothing is copied
+ * back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, mode other than board,
+ * N out of range, n_chains outside 1 .. 2^31 - 1, a negative n_segs or first_seg, seg_steps outside 1 .. 2^31,
+ * (first_seg + n_segs) seg_steps >= 2^50, table_len outside 1 .. MCQ_MAX_NFOLD_TABLE, clock_ln2 outside 0 .. 2^24, a NULL seeds,
+ * state_in, state_out or clock_table, a NULL table with n_segs > 0, a best_state that is state_in or state_out, and hist_stride below n_segs + 1
+ * when energy_hist is given.  The entries of the tables, of need_in and of events_in cannot be looked at here: they are the caller's. */
+int mcq_nfold_device(const mcq_nfold* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, same refusals; needs no GPU.  It also reads the tables and refuses a weight above
+ * 2^24, a clock_table entry above 2^26, a need_in entry >= 2^45 and a negative events_in entry.  Equal to the kernel bit for bit on
+ * every output. */
+int mcq_nfold_host(const mcq_nfold* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

@@ -130,10 +130,21 @@ MORE_FEATURES = {
     "relink3d": Feature(abi.Relink3d, "relink3d", ("relink3d_host", "relink3d_device")),
 }
 
+# The samplers added behind the searches: a third table of the same form, because tests/test_relink3d_host.py pins the keys of
+# MORE_FEATURES and the value of all_features().  lib() and the loop that makes the callables walk all three through every_feature().
+SAMPLER_FEATURES = {
+    "nfold": Feature(abi.Nfold, "nfold", ("nfold_host", "nfold_device")),
+}
+
 
 def all_features():
     """The rows of FEATURES and MORE_FEATURES, in that order."""
     return list(FEATURES.values()) + list(MORE_FEATURES.values())
+
+
+def every_feature():
+    """The rows of all three tables: all_features() and then SAMPLER_FEATURES."""
+    return all_features() + list(SAMPLER_FEATURES.values())
 
 
 def lib():
@@ -212,7 +223,7 @@ def lib():
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
-        for f in all_features():
+        for f in every_feature():
             getattr(L, f"mcq_{f.prefix}_last_error").restype = C.c_char_p
             for name in f.entries:  # (struct*) for a host entry, (struct*, hipStream_t) for a device entry
                 fn = getattr(L, "mcq_" + name)
@@ -226,7 +237,7 @@ def lib():
 
 def _raise(rc, last_error):
     """Nothing for abi.OK; otherwise the exception of a return code, with the text `last_error()` holds: the library keeps one
-    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES), and a call's text is read from its own."""
+    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES), and a call's text is read from its own."""
     if rc == abi.OK:
         return
     msg = last_error().decode(errors="replace")
@@ -261,7 +272,7 @@ def _entry(feature, name):
     return call
 
 
-for _feature in all_features():
+for _feature in every_feature():
     for _name in _feature.entries:
         globals()[_name] = _entry(_feature, _name)
 

@@ -499,6 +499,53 @@ def relink3d_lds_bytes(N, Q=None):
     return 4 * (32 + 2 * -(-cells // 32) + -(-cells // cpd) + 2 * ((Q + 1) // 2) + 2 * ((D + 1) // 2))
 
 
+MAX_NFOLD_TABLE = 128          # include/mcq.h: MCQ_MAX_NFOLD_TABLE
+NFOLD_TIME_BITS = 12           # MCQ_NFOLD_TIME_BITS: time is counted in units of 2^-12 Metropolis step
+NFOLD_WEIGHT_BITS = 24         # MCQ_NFOLD_WEIGHT_BITS: no entry of a weight row exceeds 2^24
+NFOLD_CLOCK_BITS = 26          # MCQ_NFOLD_CLOCK_BITS: no entry of the clock table exceeds 2^26
+NFOLD_NEED_BITS = 45           # MCQ_NFOLD_NEED_BITS: need < 2^45
+NFOLD_STEP_BITS = 50           # MCQ_NFOLD_STEP_BITS: (first_seg + n_segs) seg_steps < 2^50
+
+
+class Nfold(C.Structure):
+    """include/mcq.h: mcq_nfold -- the n-fold way for board placements: the Metropolis dynamics without its rejections"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_segs", C.c_int64),
+        ("first_seg", C.c_int64),
+        ("seg_steps", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("table", C.c_void_p),
+        ("table_len", C.c_int64),
+        ("clock_table", C.c_void_p),
+        ("clock_ln2", C.c_int64),
+        ("need_in", C.c_void_p),
+        ("events_in", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_step", C.c_void_p),
+        ("events_out", C.c_void_p),
+        ("n_uphill", C.c_void_p),
+        ("n_flat", C.c_void_p),
+        ("need_out", C.c_void_p),
+        ("weight_out", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+    ]
+
+
+# the per-chain outputs of an n-fold call besides the placements (state, best_state): field -> dtype ("energy_hist" has a row of
+# n_segs + 1 per chain)
+NFOLD_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "best_energy": np.int32, "best_step": np.int64, "events_out": np.int64,
+                "n_uphill": np.int64, "n_flat": np.int64, "need_out": np.uint64, "weight_out": np.uint64, "energy_hist": np.int32}
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

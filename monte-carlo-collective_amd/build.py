@@ -39,6 +39,9 @@ RELINK_SOURCES = [os.path.join(CSRC, "mcq_relink.hip")]
 # path relinking between full_3d placements, a walk over (queen, cell) pairs on one attack field and the descent of the full_3d hops
 # behind it: an eleventh list, as tests pin the ten above; compiled into the same library
 RELINK3D_SOURCES = [os.path.join(CSRC, "mcq_relink3d.hip")]
+# the n-fold way for board placements, rejection-free Metropolis dynamics as a weighted draw over the board table: a twelfth list, as
+# tests pin the eleven above; compiled into the same library
+NFOLD_SOURCES = [os.path.join(CSRC, "mcq_nfold.hip")]
 # what the sources include: the C-ABI; the chain record of the sweep and the resume kernels; the attack field of the full_3d files;
 # what the four files outside the sweep (the quenches and the heat baths) share beyond it; the lane helpers of the board heat-bath column
 # update, which the tempered sweep shares; the board table of the pair-move quench, the board hops and the board tabu search
@@ -61,7 +64,7 @@ def stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    if any(os.path.getmtime(f) > t for f in RELINK_SOURCES + RELINK3D_SOURCES):
+    if any(os.path.getmtime(f) > t for f in RELINK_SOURCES + RELINK3D_SOURCES + NFOLD_SOURCES):
         return True
     return any(os.path.getmtime(f) > t for f in SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + TABU3D_SOURCES + HEADERS)
 
@@ -71,7 +74,7 @@ def build(force=False, verbose=False):
     if not force and not stale():
         return SO
     cmd = [hipcc()] + FLAGS + ["-o", SO] + SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + TABU3D_SOURCES
-    cmd += RELINK_SOURCES + RELINK3D_SOURCES
+    cmd += RELINK_SOURCES + RELINK3D_SOURCES + NFOLD_SOURCES
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)

@@ -177,7 +177,7 @@ def _device_call(d, fn, dims, n, states, args, shapes, seeds=None, width=0, inpu
         _check_seeds(fn, seeds, n, dev)
     ins = dict(inputs() if inputs else {}, **({"seeds": seeds} if d.seeds else {}))
     st = torch.cuda.current_stream(dev) if stream is None else stream
-    tdt = {np.int32: torch.int32, np.int64: torch.int64, np.uint16: torch.int16}
+    tdt = {np.int32: torch.int32, np.int64: torch.int64, np.uint16: torch.int16, np.uint64: torch.int64}
     skip = _skip(d, shapes, figures)
     with torch.cuda.device(dev), torch.cuda.stream(st):
         q = d.block(*dims, n, *args)
