@@ -1563,6 +1563,100 @@ int mcq_nfold_device(const mcq_nfold* q, void* hip_stream);
  * every output. */
 int mcq_nfold_host(const mcq_nfold* q);
 
+/*
+ * The n-fold way for full_3d placements: the rejection-free form of the Metropolis dynamics of the reference's default move
+ * (csrc/mcq_nfold3d.hip) -- NOT a mode of the reference; never a default, like everything above that is labelled so.  mcq_nfold above
+ * keeps refusing full_3d: a queen here has N^3 - Q targets, and this block has its own entry points.  The reference draws a uniform
+ * queen and a uniform cell among the N^3 - Q cells that hold no queen (it redraws occupied cells before the step counts), so a step
+ * proposes one of M = Q (N^3 - Q) moves uniformly; this block holds the acceptance weight of all of them.  The rule is integer-exact;
+ * items 2, 4, 5, 7 and 8 of the mcq_nfold rule carry over word for word except where stated here:
+ *   1. INPUT.  state_in is uint8[n_chains][3 Q], every byte clamped to N - 1; N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D and
+ *      2 <= Q <= N^3 - 1 (n_queens = 0 means N^2).  S(t) is the number of queens that hold or attack cell t (csrc/mcq_field.h), the
+ *      attack and E are those of the mcq_quench3d rule; energy_in is the recount.  A REPEATED placement (two queens in one cell after
+ *      clamping) sets bit 0 of flags (MCQ_NFOLD3D_REPEATED) and is handed back unmoved: state_out and best_state are the clamped input,
+ *      energy_in = energy_out = best_energy = the pairwise recount (a shared cell counts as an attacking pair), energy_hist holds it
+ *      throughout, events_out is the start counter, need_out is need_in or, without one, the need drawn from block events_in[r],
+ *      weight_out, best_step, n_uphill and n_flat are 0.
+ *   2. WEIGHTS.  For queen q at p and a cell t that holds no queen:  a(q, t) = S(t) - [p attacks t],  c_q = S(p) - 1,
+ *      d = a(q, t) - c_q,  w(q, t) = T_s[min(max(d, 0), D - 1)].  Cells that hold a queen carry no weight.  R(q) = sum over t of
+ *      w(q, t) in uint64 (it reaches 2^39), W = sum over q of R(q) <= M 2^24 < 2^52.  1 <= D <= MCQ_MAX_NFOLD3D_TABLE = 512 (the
+ *      largest difference is 13 (N - 1) = 403); every entry is <= 2^24.  W / (M 2^24) is the probability that one Metropolis step of
+ *      the reference is accepted.
+ *   3. TIME.  need = M l(x2) < 2^58 (MCQ_NFOLD3D_NEED_BITS), so need << 12 no longer fits 64 bits and tau is stated as the exact
+ *      quotient:  tau = max(1, floor(need 2^12 / W)).  (64-bit arithmetic forms it as q1 = need div W, r1 = need mod W,
+ *      tau0 = q1 2^12 + floor(r1 2^12 / W) with r1 2^12 < 2^64; q1 >= 2^32 means tau > left with nothing more to compute.)  When
+ *      W > 0 and tau <= left the event fires and left -= tau; otherwise need -= floor(left W / 2^12), a 96-bit product whose quotient
+ *      is at most need (W = 0 leaves need as it is), and the segment ends.
+ *   4. DRAWS.  Block e of chain r is philox4x32-10(counter = (low 32 bits of e, high 32 bits of e, 0, 0), key = (seeds[r], 12))
+ *      (key words 0 - 11 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d, mcq_tabu, mcq_tabu3d,
+ *      mcq_relink, mcq_relink3d and mcq_nfold; 12 is this block's).  x2 gives the need as under mcq_nfold, with this M.
+ *      U = floor(X W / 2^64), X = x0 2^32 + x1, and the move is the first (q, t) whose inclusive prefix sum of w exceeds U, in the
+ *      order q ascending, then cell index (i N + j) N + k ascending over the cells that hold no queen.  x3 is unused.
+ *   5. EVENT.  Queen q moves to t, E += d, e += 1; the counters, best_energy, best_state and best_step are as under mcq_nfold.
+ *   6. OUTPUTS.  Those of mcq_nfold, and flags.
+ *   7. CUTTING A RUN.  As under mcq_nfold: a run cut at a segment boundary is the unbroken run; n_segs = 0 is a recount and a copy.
+ * Chains do not interact and a call reads all of a chain's inputs before it writes any of its outputs, so state_out may be state_in;
+ * best_state may be neither state_in nor state_out.
+ *
+ * mcq_nfold3d_device keeps a chain in the LDS of one workgroup: 2 376 dwords (reductions, the row T_s, the clock table, a histogram
+ * of S over the free cells and a sum per c_q), R(q) (a uint64 per queen), the field (one byte per cell to N = 19, 16 bits beyond),
+ * the occupancy bitmap and the queens (16 bits each), each array rounded up to a dword:
+ *   bytes = 4 (2376 + 2 Q + ceil(N^3 / (4 or 2)) + ceil(N^3 / 32) + ceil(Q / 2)) <= MCQ_MAX_NFOLD3D_LDS.
+ * Every Q = N^2 fits (89 376 bytes at N = 32); at N = 32 the largest Q is 8 470.  mcq_nfold3d_host runs every shape.
+ */
+#define MCQ_MAX_NFOLD3D_TABLE 512 /* the largest table_len of mcq_nfold3d, as MCQ_MAX_HEATBATH_TABLE: 13 (MCQ_MAX_N_QUENCH3D - 1) = 403 is the largest difference */
+#define MCQ_NFOLD3D_NEED_BITS 58  /* need < 2^58 */
+#define MCQ_MAX_NFOLD3D_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_nfold3d_device may take */
+#define MCQ_NFOLD3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) input hold the same cell; nothing was moved */
+typedef struct mcq_nfold3d {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t mode;           /* MCQ_MODE_FULL3D; anything else is MCQ_EINVAL (boards are mcq_nfold's) */
+    int32_t n_queens;       /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_segs;         /* >= 0; 0 = a recount and a copy */
+    int64_t first_seg;      /* >= 0: the global index of the call's first segment */
+    int64_t seg_steps;      /* 1 .. 2^31 Metropolis steps per segment; (first_seg + n_segs) seg_steps < 2^50 */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint32_t* table;  /* [n_segs][table_len]: the weight rows, every entry <= 2^24; may be NULL when n_segs = 0 */
+    int64_t table_len;      /* D: 1 .. MCQ_MAX_NFOLD3D_TABLE */
+    const uint32_t* clock_table; /* [256]: every entry <= 2^26 */
+    int64_t clock_ln2;      /* 0 .. 2^24 */
+    const uint64_t* need_in; /* optional [n_chains]: the hazard left from the piece before, each < 2^58; NULL: drawn from block events_in[r] */
+    const int64_t* events_in; /* optional [n_chains]: the event counters the chains start at, each >= 0; NULL: 0 */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;     /* [n_chains][Q][3]; may be state_in */
+    uint8_t* best_state;    /* optional [n_chains][Q][3]; neither state_in nor state_out */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;    /* optional [n_chains] */
+    int32_t* best_energy;   /* optional [n_chains] */
+    int64_t* best_step;     /* optional [n_chains]: the Metropolis step of the call at which best_energy was first reached; 0 = the input */
+    int64_t* events_out;    /* optional [n_chains]: the event counter behind the call */
+    int64_t* n_uphill;      /* optional [n_chains]: events of this call with d > 0 */
+    int64_t* n_flat;        /* optional [n_chains]: events of this call with d = 0 */
+    uint64_t* need_out;     /* optional [n_chains] */
+    uint64_t* weight_out;   /* optional [n_chains]: W of the output under the last row; 0 when n_segs = 0 */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_segs */
+    int64_t hist_stride;    /* >= n_segs + 1 when energy_hist is given; not read otherwise */
+    int32_t* flags;         /* optional [n_chains]: MCQ_NFOLD3D_* */
+} mcq_nfold3d;
+
+/* the message of the last error of the calling thread from the two mcq_nfold3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_nfold3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_segs is; asynchronous: nothing is copied
+ * back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, a mode other than
+ * full_3d, N outside 2 .. 32 (33 .. 64 named as this build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside
+ * 1 .. 2^31 - 1, a negative n_segs or first_seg, seg_steps outside 1 .. 2^31, (first_seg + n_segs) seg_steps >= 2^50, table_len
+ * outside 1 .. MCQ_MAX_NFOLD3D_TABLE, clock_ln2 outside 0 .. 2^24, a NULL seeds, state_in, state_out or clock_table, a NULL table with
+ * n_segs > 0, a best_state that is state_in or state_out, hist_stride below n_segs + 1 when energy_hist is given, and any (N, Q)
+ * whose chain exceeds MCQ_MAX_NFOLD3D_LDS (the message names N, Q and the bytes).  The entries of the tables, of need_in and of
+ * events_in cannot be looked at here: they are the caller's. */
+int mcq_nfold3d_device(const mcq_nfold3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers, for every shape (no LDS here), otherwise the same refusals; needs no GPU.  It
+ * also reads the tables and refuses a weight above 2^24, a clock_table entry above 2^26, a need_in entry >= 2^58 and a negative
+ * events_in entry.  It follows the definition -- every (q, t) pair behind every event -- and is equal to the kernel bit for bit on
+ * every output. */
+int mcq_nfold3d_host(const mcq_nfold3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

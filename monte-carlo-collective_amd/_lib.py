@@ -137,6 +137,13 @@ SAMPLER_FEATURES = {
 }
 
 
+# The forms of the samplers for full_3d placements: a fourth table of the same form, because tests/test_nfold_host.py pins the keys of
+# SAMPLER_FEATURES and the value of every_feature().  lib() and the loop that makes the callables walk all four through bound_features().
+SAMPLER3D_FEATURES = {
+    "nfold3d": Feature(abi.Nfold3d, "nfold3d", ("nfold3d_host", "nfold3d_device")),
+}
+
+
 def all_features():
     """The rows of FEATURES and MORE_FEATURES, in that order."""
     return list(FEATURES.values()) + list(MORE_FEATURES.values())
@@ -145,6 +152,11 @@ def all_features():
 def every_feature():
     """The rows of all three tables: all_features() and then SAMPLER_FEATURES."""
     return all_features() + list(SAMPLER_FEATURES.values())
+
+
+def bound_features():
+    """The rows of all four tables: every_feature() and then SAMPLER3D_FEATURES.  What lib() declares and what has a callable here."""
+    return every_feature() + list(SAMPLER3D_FEATURES.values())
 
 
 def lib():
@@ -223,7 +235,7 @@ def lib():
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
-        for f in every_feature():
+        for f in bound_features():
             getattr(L, f"mcq_{f.prefix}_last_error").restype = C.c_char_p
             for name in f.entries:  # (struct*) for a host entry, (struct*, hipStream_t) for a device entry
                 fn = getattr(L, "mcq_" + name)
@@ -237,7 +249,7 @@ def lib():
 
 def _raise(rc, last_error):
     """Nothing for abi.OK; otherwise the exception of a return code, with the text `last_error()` holds: the library keeps one
-    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES), and a call's text is read from its own."""
+    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES, SAMPLER3D_FEATURES), and a call's text is read from its own."""
     if rc == abi.OK:
         return
     msg = last_error().decode(errors="replace")
@@ -272,7 +284,7 @@ def _entry(feature, name):
     return call
 
 
-for _feature in every_feature():
+for _feature in bound_features():
     for _name in _feature.entries:
         globals()[_name] = _entry(_feature, _name)
 

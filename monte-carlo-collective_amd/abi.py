@@ -546,6 +546,60 @@ NFOLD_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "best_energy": np
                 "n_uphill": np.int64, "n_flat": np.int64, "need_out": np.uint64, "weight_out": np.uint64, "energy_hist": np.int32}
 
 
+MAX_NFOLD3D_TABLE = 512        # include/mcq.h: MCQ_MAX_NFOLD3D_TABLE
+NFOLD3D_NEED_BITS = 58         # MCQ_NFOLD3D_NEED_BITS: need < 2^58
+MAX_NFOLD3D_LDS = 160 * 1024   # MCQ_MAX_NFOLD3D_LDS
+NFOLD3D_REPEATED = 1           # MCQ_NFOLD3D_REPEATED: bit 0 of flags
+
+
+class Nfold3d(C.Structure):
+    """include/mcq.h: mcq_nfold3d -- the n-fold way for full_3d placements: the Metropolis dynamics of a queen's move to a free cell without its rejections"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_segs", C.c_int64),
+        ("first_seg", C.c_int64),
+        ("seg_steps", C.c_int64),
+        ("seeds", C.c_void_p),
+        ("table", C.c_void_p),
+        ("table_len", C.c_int64),
+        ("clock_table", C.c_void_p),
+        ("clock_ln2", C.c_int64),
+        ("need_in", C.c_void_p),
+        ("events_in", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_step", C.c_void_p),
+        ("events_out", C.c_void_p),
+        ("n_uphill", C.c_void_p),
+        ("n_flat", C.c_void_p),
+        ("need_out", C.c_void_p),
+        ("weight_out", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d n-fold call besides the placements (state, best_state): field -> dtype ("energy_hist" has a row of
+# n_segs + 1 per chain)
+NFOLD3D_DTYPES = dict(NFOLD_DTYPES, flags=np.int32)
+
+
+def nfold3d_lds_bytes(N, Q=None):
+    """The bytes of LDS a chain of mcq_nfold3d_device takes (include/mcq.h, below the rule): it runs what stays within MAX_NFOLD3D_LDS."""
+    N = int(N)
+    Q = N * N if Q is None or int(Q) == 0 else int(Q)
+    cells, cpd = N ** 3, 4 if N <= 19 else 2
+    return 4 * (2376 + 2 * Q + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2)
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device
