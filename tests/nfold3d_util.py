@@ -59,7 +59,8 @@ def weights(N, z, row):
 
 def nfold(N, placement, seed, tables, seg_steps, clock, first_seg=0, need_in=None, events_in=0, trace=None):
     """One placement through the rule; returns a dict with the fields of mcq_nfold3d plus `energy_hist`.  `trace` (a list) receives
-    (segment, left, q, t, d, tau, U, W) of every event."""
+    (segment, left, q, t, d, tau, U, W, lo, hi, zero_before) of every event: the chosen move holds the integers lo <= U < hi of
+    0 .. W - 1, and zero_before says whether the move before it in walk order (q ascending, free cells ascending) has weight 0."""
     ln2, ct = clock
     z = q3.clamp(N, placement).copy()
     Q, C = len(z), N ** 3
@@ -95,17 +96,24 @@ def nfold(N, placement, seed, tables, seg_steps, clock, first_seg=0, need_in=Non
                 break
             left -= tau
             U = (((x[0] << 32) | x[1]) * W) >> 64
-            flat_index = int(np.searchsorted(np.cumsum(w.reshape(-1)), U, side="right"))  # the first inclusive prefix sum above U
+            sums = np.cumsum(w.reshape(-1))
+            flat_index = int(np.searchsorted(sums, U, side="right"))  # the first inclusive prefix sum above U
             q, t = divmod(flat_index, C)
             assert w[q, t] > 0
             dd = int(d[q, t])
+            if trace is not None:
+                held = set(int(v) for v in index_of(N, z))
+                before = flat_index - 1
+                while before >= 0 and before % C in held:
+                    before -= 1
+                trace_tail = (int(sums[flat_index]) - int(w[q, t]), int(sums[flat_index]), bool(before >= 0 and w.reshape(-1)[before] == 0))
             z[q] = (t // (N * N), (t // N) % N, t % N)
             E += dd
             up += dd > 0
             flat += dd == 0
             e += 1
             if trace is not None:
-                trace.append((s, left, q, t, dd, tau, U, W))
+                trace.append((s, left, q, t, dd, tau, U, W) + trace_tail)
             if E < best_e:
                 best_e, best_step, best = E, s * int(seg_steps) + ((whole - left) >> TIME_BITS), z.copy()
             x = block(seed, e)
@@ -117,11 +125,17 @@ def nfold(N, placement, seed, tables, seg_steps, clock, first_seg=0, need_in=Non
             "weight_out": W if len(tables) else 0, "flags": 0, "energy_hist": np.array(hist, dtype=np.int64)}
 
 
-def nfold_many(N, states, seeds, tables, seg_steps, clock, Q=None, first_seg=0, need_in=None, events_in=None):
-    """nfold over the rows of `states`, stacked like the library's outputs."""
+def _trace_of(traces):
+    traces.append([])
+    return traces[-1]
+
+
+def nfold_many(N, states, seeds, tables, seg_steps, clock, Q=None, first_seg=0, need_in=None, events_in=None, traces=None):
+    """nfold over the rows of `states`, stacked like the library's outputs.  `traces` (a list) receives the trace of every chain."""
     Q = N * N if Q is None else Q
     rows = [nfold(N, s, int(seeds[r]), tables, seg_steps, clock, first_seg, None if need_in is None else int(need_in[r]),
-                  0 if events_in is None else int(events_in[r])) for r, s in enumerate(np.asarray(states).reshape(-1, 3 * Q))]
+                  0 if events_in is None else int(events_in[r]), None if traces is None else _trace_of(traces))
+            for r, s in enumerate(np.asarray(states).reshape(-1, 3 * Q))]
     return {k: np.stack([np.asarray(r[k]) for r in rows]) for k in FIELDS + ("energy_hist",)}
 
 

@@ -49,7 +49,8 @@ def weights(N, h, row):
 
 def nfold(N, board, seed, tables, seg_steps, clock, first_seg=0, need_in=None, events_in=0, trace=None):
     """One board through the rule; returns a dict with the fields of mcq_nfold plus `energy_hist`.  `trace` (a list) receives
-    (segment, left, c, k, d) of every event."""
+    (segment, left, c, k, d, U, W, lo, hi, zero_before) of every event: the chosen move holds the integers lo <= U < hi of 0 .. W - 1,
+    and zero_before says whether the move before it in walk order (c ascending, k ascending, k = h(c) skipped) has weight 0."""
     ln2, ct = clock
     h = qu.clamp(N, board).copy()
     Q, M = N * N, N * N * (N - 1)
@@ -79,17 +80,23 @@ def nfold(N, board, seed, tables, seg_steps, clock, first_seg=0, need_in=None, e
                 break
             left -= tau
             U = (((x[0] << 32) | x[1]) * W) >> 64
-            flat_index = int(np.searchsorted(np.cumsum(w.reshape(-1)), U, side="right"))  # the first inclusive prefix sum above U
+            sums = np.cumsum(w.reshape(-1))
+            flat_index = int(np.searchsorted(sums, U, side="right"))  # the first inclusive prefix sum above U
             c, k = divmod(flat_index, N)
             assert k != h[c] and w[c, k] > 0
             dd = int(d[c, k])
+            if trace is not None:
+                before = flat_index - 1
+                while before >= 0 and before % N == h[before // N]:
+                    before -= 1
+                trace_tail = (U, W, int(sums[flat_index]) - int(w[c, k]), int(sums[flat_index]), bool(before >= 0 and w.reshape(-1)[before] == 0))
             h[c] = k
             E += dd
             up += dd > 0
             flat += dd == 0
             e += 1
             if trace is not None:
-                trace.append((s, left, c, k, dd))
+                trace.append((s, left, c, k, dd) + trace_tail)
             if E < best_e:
                 best_e, best_step, best = E, s * int(seg_steps) + ((whole - left) >> TIME_BITS), h.copy()
             x = block(seed, e)
@@ -101,10 +108,16 @@ def nfold(N, board, seed, tables, seg_steps, clock, first_seg=0, need_in=None, e
             "energy_hist": np.array(hist, dtype=np.int64)}
 
 
-def nfold_many(N, states, seeds, tables, seg_steps, clock, first_seg=0, need_in=None, events_in=None):
-    """nfold over the rows of `states`, stacked like the library's outputs."""
+def _trace_of(traces):
+    traces.append([])
+    return traces[-1]
+
+
+def nfold_many(N, states, seeds, tables, seg_steps, clock, first_seg=0, need_in=None, events_in=None, traces=None):
+    """nfold over the rows of `states`, stacked like the library's outputs.  `traces` (a list) receives the trace of every chain."""
     rows = [nfold(N, s, int(seeds[r]), tables, seg_steps, clock, first_seg, None if need_in is None else int(need_in[r]),
-                  0 if events_in is None else int(events_in[r])) for r, s in enumerate(np.asarray(states).reshape(-1, N * N))]
+                  0 if events_in is None else int(events_in[r]), None if traces is None else _trace_of(traces))
+            for r, s in enumerate(np.asarray(states).reshape(-1, N * N))]
     return {k: np.stack([np.asarray(r[k]) for r in rows]) for k in FIELDS + ("energy_hist",)}
 
 
