@@ -1657,6 +1657,98 @@ int mcq_nfold3d_device(const mcq_nfold3d* q, void* hip_stream);
  * every output. */
 int mcq_nfold3d_host(const mcq_nfold3d* q);
 
+/*
+ * Extremal optimisation of board placements (Boettcher and Percus, tau-EO): every iteration ranks the columns by their local
+ * badness, draws a rank from a table and moves that column UNCONDITIONALLY (csrc/mcq_eo.hip) -- NOT a mode of the reference; never a
+ * default, like everything above that is labelled so.  Every search above chooses a move by the energy change it causes and the
+ * samplers choose by a temperature; this block has no temperature, no memory and no acceptance test.  Boards only.  The rule is
+ * integer-exact:
+ *   1. SETUP.  Every input byte is clamped to N - 1 first; a(c, k) and E are those of the mcq_quench rule, items 1 - 2.
+ *      lambda(c) = a(c, h(c)) <= 4 (N - 1) is the local badness of column c.  No local search is applied to the input; energy_in
+ *      is its recount.
+ *   2. CHAIN STATE: the placement, the run's best energy B and the iteration index; nothing else.  A call runs the iterations
+ *      t = 0 .. n_iters - 1; iteration t has the GLOBAL index g = first_iter + t.  B = min(best_floor[r], energy_in), or energy_in
+ *      without best_floor.
+ *   3. RANDOM WORDS.  Iteration g draws one block (x0, x1, x2, x3) =
+ *        philox4x32-10(counter = (low 32 bits of g, high bits of g, 0, 0), key = (seeds[r], 13))
+ *      (key words 0 - 12 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d, mcq_tabu,
+ *      mcq_tabu3d, mcq_relink, mcq_relink3d, mcq_nfold and mcq_nfold3d; this block's is 13).  o = floor(x1 N^2 / 2^32) is the tie
+ *      offset of the columns and oh = floor(x2 N / 2^32) that of the heights.
+ *   4. RANK.  rank_cdf is uint32[n_ranks], ONE table for all chains, 0 <= n_ranks <= N^2 - 1.  j = #{ i < n_ranks :
+ *      rank_cdf[i] <= x0 }, so 0 <= j <= n_ranks.  The count is defined for any table; a table that does not decrease makes it the
+ *      draw from a cumulative distribution over the ranks 0 .. n_ranks.  n_ranks = 0 gives j = 0 in every iteration.
+ *   5. COLUMN.  All N^2 columns are ordered by (-lambda(c), rho(c)) ascending, rho(c) = (c - o) mod N^2: the worst first, equal
+ *      lambda broken by a random rotation, so that no column order is favoured.  The iteration moves the column c at position j.  A
+ *      column with lambda(c) = 0 may be drawn and moves like any other (n_free counts those moves).  With E = 0 the iteration
+ *      moves nothing and counts in n_idle; that lasts forever.
+ *   6. HEIGHT of the column c.  move = MCQ_EO_MOVE_BEST: the k != h(c) with the lexicographically smallest
+ *      (a(c, k), (k - oh) mod N).  move = MCQ_EO_MOVE_RANDOM: k' = floor(x3 (N - 1) / 2^32) and k = k' + [k' >= h(c)].
+ *      delta = a(c, k) - lambda(c).  The move is always taken: h(c) = k and E += delta.
+ *   7. BEST, COUNTERS, OUTPUTS as in the mcq_tabu rule, items 5 - 6.  A move with E + delta < B sets B, best_iter = t + 1 and the
+ *      best placement; best_iter is relative to the call, 0 means the input or an earlier call.  Counters, all int64: n_moves;
+ *      n_uphill, the moves with delta > 0; n_flat, those with delta = 0; n_free, those of a column with lambda = 0; n_idle.
+ *      energy_hist[r][0 .. n_iters] holds energy_in, then E after each iteration.  energy_out = E and state_out are those behind the
+ *      last iteration.  best_energy = B.  best_state is the best placement of THIS call: when no move of the call went below B it is
+ *      the (clamped) input placement, and best_energy = B <= energy_in says whether that placement has it.
+ * Bounds: first_iter + n_iters < 2^63; move is MCQ_EO_MOVE_BEST or MCQ_EO_MOVE_RANDOM.
+ * Consequences:
+ *   (a) n_iters = 0 is the recount: state_out and best_state are the clamped input, energy_out = energy_in, best_energy = B, every
+ *       counter 0.
+ *   (b) a run cut into calls is the unbroken run on every output, when each call is fed state_out as state_in, best_energy as
+ *       best_floor and first_iter carried over -- there is nothing else to carry; the pieces combine as under mcq_tabu (b).
+ *   (c) state_out may be state_in; best_state may be neither state_in nor state_out.
+ *   (d) with n_ranks = 0 and move = MCQ_EO_MOVE_BEST nothing but the ties is random: the worst column takes its best other height.
+ * N = MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS on the device and in host code alike.  Chains do not interact and a call reads all of a
+ * chain's inputs before it writes any of its outputs.
+ *
+ * mcq_eo_device keeps a chain in the LDS of one wavefront: the table a(c, k) as bytes in rows of 4 ((NP / 4) | 1) bytes, the
+ * heights, the best placement and NP^2 dwords for rank_cdf, NP = N rounded up to 4, 8, 12, 16, 24 or 32:
+ *   bytes = NP^2 (4 ((NP / 4) | 1) + 6),  43 008 at NP = 32 (three chains per compute unit), <= MCQ_MAX_EO_LDS.
+ */
+#define MCQ_EO_MOVE_BEST 0
+#define MCQ_EO_MOVE_RANDOM 1
+#define MCQ_MAX_EO_LDS (64 * 1024) /* bytes of LDS a workgroup of mcq_eo_device may take */
+typedef struct mcq_eo {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH_PAIRS */
+    int32_t mode;           /* MCQ_MODE_BOARD; anything else is MCQ_EINVAL */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_iters;        /* >= 0; 0 = the recount */
+    int64_t first_iter;     /* >= 0: the global index of the call's first iteration; first_iter + n_iters < 2^63 */
+    int32_t move;           /* MCQ_EO_MOVE_BEST or MCQ_EO_MOVE_RANDOM */
+    int32_t n_ranks;        /* 0 .. N^2 - 1: the entries of rank_cdf */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint32_t* rank_cdf; /* [n_ranks], one table for all chains; may be NULL when n_ranks = 0 */
+    const uint8_t* state_in; /* [n_chains][N*N], final_state layout */
+    uint8_t* state_out;     /* [n_chains][N*N]; may be state_in */
+    const int32_t* best_floor; /* optional [n_chains]: the best energy of the calls before */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* best_energy;   /* optional [n_chains]: B */
+    int64_t* best_iter;     /* optional [n_chains]: 0 = no move of the call went below B, t + 1 = behind iteration t of the call */
+    uint8_t* best_state;    /* optional [n_chains][N*N]; neither state_in nor state_out */
+    int64_t* n_moves;       /* optional [n_chains] */
+    int64_t* n_uphill;      /* optional [n_chains]: moves with delta > 0 */
+    int64_t* n_flat;        /* optional [n_chains]: moves with delta = 0 */
+    int64_t* n_free;        /* optional [n_chains]: moves of a column with lambda = 0 */
+    int64_t* n_idle;        /* optional [n_chains]: iterations at E = 0, which move nothing */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_iters */
+    int64_t hist_stride;    /* >= n_iters + 1 when energy_hist is given; not read otherwise */
+} mcq_eo;
+
+/* the message of the last error of the calling thread from the two mcq_eo_* calls below (they do not set mcq_last_error()) */
+const char* mcq_eo_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_iters is; asynchronous: nothing is
+ * copied back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, mode other than
+ * board, N out of range, n_chains outside 1 .. 2^31 - 1, a negative n_iters or first_iter, first_iter + n_iters >= 2^63, a move
+ * other than the two above, n_ranks outside 0 .. N^2 - 1, a NULL rank_cdf with n_ranks > 0, a NULL seeds, state_in or state_out,
+ * hist_stride below n_iters + 1 when energy_hist is given, a best_state that is state_in or state_out, and a chain above
+ * MCQ_MAX_EO_LDS (no N in range is).  The entries of rank_cdf cannot be looked at here: they are the caller's, and the count of
+ * item 4 is defined for any of them. */
+int mcq_eo_device(const mcq_eo* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers -- an explicit stable sort of the columns in every iteration --, same refusals;
+ * needs no GPU.  It also reads rank_cdf and refuses a table that decreases.  Equal to the kernel bit for bit on every output. */
+int mcq_eo_host(const mcq_eo* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

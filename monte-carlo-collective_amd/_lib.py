@@ -144,6 +144,14 @@ SAMPLER3D_FEATURES = {
 }
 
 
+# The searches added behind the samplers: a fifth table of the same form, because tests/test_nfold3d_host.py pins the keys of
+# SAMPLER3D_FEATURES and the value of bound_features().  lib() and the loop that makes the callables walk all five through
+# declared_features(); a new search goes here.
+SEARCH_FEATURES = {
+    "eo": Feature(abi.Eo, "eo", ("eo_host", "eo_device")),
+}
+
+
 def all_features():
     """The rows of FEATURES and MORE_FEATURES, in that order."""
     return list(FEATURES.values()) + list(MORE_FEATURES.values())
@@ -155,8 +163,13 @@ def every_feature():
 
 
 def bound_features():
-    """The rows of all four tables: every_feature() and then SAMPLER3D_FEATURES.  What lib() declares and what has a callable here."""
+    """The rows of the first four tables: every_feature() and then SAMPLER3D_FEATURES."""
     return every_feature() + list(SAMPLER3D_FEATURES.values())
+
+
+def declared_features():
+    """The rows of all five tables: bound_features() and then SEARCH_FEATURES.  What lib() declares and what has a callable here."""
+    return bound_features() + list(SEARCH_FEATURES.values())
 
 
 def lib():
@@ -235,7 +248,7 @@ def lib():
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
-        for f in bound_features():
+        for f in declared_features():
             getattr(L, f"mcq_{f.prefix}_last_error").restype = C.c_char_p
             for name in f.entries:  # (struct*) for a host entry, (struct*, hipStream_t) for a device entry
                 fn = getattr(L, "mcq_" + name)
@@ -249,7 +262,7 @@ def lib():
 
 def _raise(rc, last_error):
     """Nothing for abi.OK; otherwise the exception of a return code, with the text `last_error()` holds: the library keeps one
-    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES, SAMPLER3D_FEATURES), and a call's text is read from its own."""
+    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES, SAMPLER3D_FEATURES, SEARCH_FEATURES), and a call's text is read from its own."""
     if rc == abi.OK:
         return
     msg = last_error().decode(errors="replace")
@@ -284,7 +297,7 @@ def _entry(feature, name):
     return call
 
 
-for _feature in bound_features():
+for _feature in declared_features():
     for _name in _feature.entries:
         globals()[_name] = _entry(_feature, _name)
 

@@ -600,6 +600,53 @@ def nfold3d_lds_bytes(N, Q=None):
     return 4 * (2376 + 2 * Q + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2)
 
 
+EO_MOVE_BEST = 0               # include/mcq.h: MCQ_EO_MOVE_BEST
+EO_MOVE_RANDOM = 1             # MCQ_EO_MOVE_RANDOM
+MAX_EO_LDS = 64 * 1024         # MCQ_MAX_EO_LDS
+
+
+class Eo(C.Structure):
+    """include/mcq.h: mcq_eo -- extremal optimisation of board placements: the column at a drawn rank of local badness moves, whatever it costs"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("mode", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_iters", C.c_int64),
+        ("first_iter", C.c_int64),
+        ("move", C.c_int32),
+        ("n_ranks", C.c_int32),
+        ("seeds", C.c_void_p),
+        ("rank_cdf", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("best_floor", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_iter", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_uphill", C.c_void_p),
+        ("n_flat", C.c_void_p),
+        ("n_free", C.c_void_p),
+        ("n_idle", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+    ]
+
+
+# the per-chain outputs of an extremal-optimisation call besides the placements (state, best_state): field -> dtype ("energy_hist" has
+# a row of n_iters + 1 per chain)
+EO_DTYPES = {"energy_in": np.int32, "energy_out": np.int32, "best_energy": np.int32, "best_iter": np.int64, "n_moves": np.int64,
+             "n_uphill": np.int64, "n_flat": np.int64, "n_free": np.int64, "n_idle": np.int64, "energy_hist": np.int32}
+
+
+def eo_lds_bytes(N):
+    """The bytes of LDS a chain of mcq_eo_device takes (include/mcq.h, below the rule): table, heights, best placement and rank_cdf."""
+    NP = next(p for p in (4, 8, 12, 16, 24, 32) if int(N) <= p)
+    return NP * NP * (4 * ((NP // 4) | 1) + 6)
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device
