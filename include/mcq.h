@@ -1749,6 +1749,108 @@ int mcq_eo_device(const mcq_eo* q, void* hip_stream);
  * needs no GPU.  It also reads rank_cdf and refuses a table that decreases.  Equal to the kernel bit for bit on every output. */
 int mcq_eo_host(const mcq_eo* q);
 
+/*
+ * Extremal optimisation of full_3d placements: every iteration ranks the QUEENS by their local badness, draws a rank from a table and
+ * moves that queen UNCONDITIONALLY to a free cell of the cube (csrc/mcq_eo3d.hip) -- NOT a mode of the reference; never a default, like
+ * everything above that is labelled so.  mcq_eo above keeps refusing full_3d: a queen here has N^3 targets and no column of its own,
+ * and this block has its own entry points.  The rule is integer-exact:
+ *   1. SETUP.  The placement (Q triples of bytes, 3 Q bytes per chain), the clamping to N - 1, REPEATED, a(q, t) and E are those of
+ *      the mcq_quench3d rule, items 1 - 2, exactly as mcq_tabu3d item 1 takes them.  N = 2 .. MCQ_MAX_N_QUENCH3D and
+ *      2 <= Q <= N^3 - 1 (n_queens = 0 means N^2).  C = N^3; a cell is FREE when it holds no queen, so there are F = C - Q >= 1 free
+ *      cells.  lambda(q) = a(q, pos(q)) <= 13 (N - 1) is the local badness of queen q.  No local search is applied to the input;
+ *      energy_in is its recount.
+ *   2. CHAIN STATE: the placement, the run's best energy B and the iteration index; nothing else.  A call runs the iterations
+ *      t = 0 .. n_iters - 1; iteration t has the GLOBAL index g = first_iter + t.  B = min(best_floor[r], energy_in), or energy_in
+ *      without best_floor.
+ *   3. RANDOM WORDS.  Iteration g draws one block (x0, x1, x2, x3) =
+ *        philox4x32-10(counter = (low 32 bits of g, high bits of g, 0, 0), key = (seeds[r], 14))
+ *      (key words 0 - 13 are taken by the sweep, the two heat baths, the two tempered sweeps, mcq_hop, mcq_hop3d, mcq_tabu,
+ *      mcq_tabu3d, mcq_relink, mcq_relink3d, mcq_nfold, mcq_nfold3d and mcq_eo; this block's is 14).  x0 draws the rank;
+ *      o_q = floor(x1 Q / 2^32) and o_t = floor(x2 C / 2^32) are the tie offsets of the queens and of the cells; x3 draws the random
+ *      target.
+ *   4. RANK.  rank_cdf is uint32[n_ranks], ONE table for all chains, 0 <= n_ranks <= Q - 1.  j = #{ i < n_ranks :
+ *      rank_cdf[i] <= x0 }, so 0 <= j <= n_ranks.  The count is defined for any table; a table that does not decrease makes it the
+ *      draw from a cumulative distribution over the ranks 0 .. n_ranks.  n_ranks = 0 gives j = 0 in every iteration.
+ *   5. QUEEN.  All Q queens are ordered by (-lambda(q), rho_q) ascending, rho_q = (q - o_q) mod Q: the worst first, equal lambda
+ *      broken by a random rotation, so that no queen order is favoured.  The iteration moves the queen q at position j.  A queen with
+ *      lambda(q) = 0 may be drawn and moves like any other (n_free counts those moves).  With E = 0 the iteration moves nothing and
+ *      counts in n_idle; that lasts forever.
+ *   6. TARGET of the queen q at p = pos(q).  move = MCQ_EO3D_MOVE_BEST: the free cell t with the lexicographically smallest
+ *      (a(q, t), rho_t), rho_t = (t - o_t) mod C, t the cell index i N^2 + j N + k.  move = MCQ_EO3D_MOVE_RANDOM:
+ *      m = floor(x3 F / 2^32), and t is the free cell that has exactly m free cells of smaller index: uniform over the free cells.
+ *      p holds a queen, so it is never a target.  delta = a(q, t) - lambda(q).  The move is always taken: pos(q) = t and E += delta.
+ *   7. BEST, COUNTERS, OUTPUTS as in the mcq_eo rule, item 7: a move with E + delta < B sets B, best_iter = t + 1 and the best
+ *      placement; best_iter is relative to the call, 0 means the input or an earlier call.  Counters, all int64: n_moves; n_uphill,
+ *      the moves with delta > 0; n_flat, those with delta = 0; n_free, those of a queen with lambda = 0; n_idle.
+ *      energy_hist[r][0 .. n_iters] holds energy_in, then E after each iteration.  energy_out = E and state_out are those behind the
+ *      last iteration.  best_energy = B.  best_state is the best placement of THIS call: when no move of the call went below B it is
+ *      the (clamped) input placement.  A REPEATED input (two queens in one cell after clamping) sets bit 0 of flags
+ *      (MCQ_EO3D_REPEATED) and is handed back unmoved: state_out and best_state are the clamped input, energy_in = energy_out =
+ *      best_energy = the recount (a shared cell counts as an attacking pair; best_floor is not looked at), every counter and best_iter
+ *      are 0, and energy_hist[0 .. n_iters] all hold the recount.  No output of the rule is such a placement.
+ * Bounds: first_iter + n_iters < 2^63; move is MCQ_EO3D_MOVE_BEST or MCQ_EO3D_MOVE_RANDOM.
+ * Consequences:
+ *   (a) n_iters = 0 is the recount: state_out and best_state are the clamped input, energy_out = energy_in, best_energy = B, every
+ *       counter 0.
+ *   (b) a run cut into calls is the unbroken run on every output, when each call is fed state_out as state_in, best_energy as
+ *       best_floor and first_iter carried over -- there is nothing else to carry; the pieces combine as under mcq_tabu (b).
+ *   (c) state_out may be state_in; best_state may be neither state_in nor state_out.
+ *   (d) with n_ranks = 0 and move = MCQ_EO3D_MOVE_BEST nothing but the ties is random: the worst queen takes its best free cell.
+ * Chains do not interact and a call reads all of a chain's inputs before it writes any of its outputs.
+ *
+ * mcq_eo3d_device keeps a chain in the LDS of one workgroup: 480 dwords (two of 32 for the reductions and 416 bins of lambda), the
+ * field (one byte per cell to N = 19, 16 bits beyond), the occupancy bitmap and the queens (16 bits each), each array rounded up to a
+ * dword; rank_cdf stays in global memory:
+ *   bytes = 4 (480 + ceil(N^3 / (4 or 2)) + ceil(N^3 / 32) + ceil(Q / 2)) <= MCQ_MAX_EO3D_LDS.
+ * Every shape fits: 137 088 bytes at N = 32 with Q = N^3 - 1.
+ */
+#define MCQ_EO3D_MOVE_BEST 0
+#define MCQ_EO3D_MOVE_RANDOM 1
+#define MCQ_MAX_EO3D_LDS (160 * 1024) /* bytes of LDS a workgroup of mcq_eo3d_device may take */
+#define MCQ_EO3D_REPEATED 1 /* flags bit 0: two queens of the (clamped) input hold the same cell; nothing was moved */
+typedef struct mcq_eo3d {
+    int32_t N;              /* MCQ_MIN_N .. MCQ_MAX_N_QUENCH3D */
+    int32_t n_queens;       /* Q: 2 .. N^3 - 1; 0 = N^2 */
+    int64_t n_chains;       /* 1 .. 2^31 - 1 */
+    int64_t n_iters;        /* >= 0; 0 = the recount */
+    int64_t first_iter;     /* >= 0: the global index of the call's first iteration; first_iter + n_iters < 2^63 */
+    int32_t move;           /* MCQ_EO3D_MOVE_BEST or MCQ_EO3D_MOVE_RANDOM */
+    int32_t n_ranks;        /* 0 .. Q - 1: the entries of rank_cdf */
+    const uint32_t* seeds;  /* [n_chains] */
+    const uint32_t* rank_cdf; /* [n_ranks], one table for all chains; may be NULL when n_ranks = 0 */
+    const uint8_t* state_in; /* [n_chains][Q][3], final_state layout of full_3d */
+    uint8_t* state_out;     /* [n_chains][Q][3]; may be state_in */
+    const int32_t* best_floor; /* optional [n_chains]: the best energy of the calls before */
+    int32_t* energy_in;     /* optional [n_chains]: E of the (clamped) input, recounted */
+    int32_t* energy_out;    /* optional [n_chains]: E of the output */
+    int32_t* best_energy;   /* optional [n_chains]: B */
+    int64_t* best_iter;     /* optional [n_chains]: 0 = no move of the call went below B, t + 1 = behind iteration t of the call */
+    uint8_t* best_state;    /* optional [n_chains][Q][3]; neither state_in nor state_out */
+    int64_t* n_moves;       /* optional [n_chains] */
+    int64_t* n_uphill;      /* optional [n_chains]: moves with delta > 0 */
+    int64_t* n_flat;        /* optional [n_chains]: moves with delta = 0 */
+    int64_t* n_free;        /* optional [n_chains]: moves of a queen with lambda = 0 */
+    int64_t* n_idle;        /* optional [n_chains]: iterations at E = 0, which move nothing */
+    int32_t* energy_hist;   /* optional [n_chains][hist_stride]: entries 0 .. n_iters */
+    int64_t hist_stride;    /* >= n_iters + 1 when energy_hist is given; not read otherwise */
+    int32_t* flags;         /* optional [n_chains]: MCQ_EO3D_* */
+} mcq_eo3d;
+
+/* the message of the last error of the calling thread from the two mcq_eo3d_* calls below (they do not set mcq_last_error()) */
+const char* mcq_eo3d_last_error(void);
+/* Every pointer of `q` is a DEVICE pointer.  One kernel enqueued on `hip_stream`, whatever n_iters is; asynchronous: nothing is
+ * copied back and nothing synchronises.  MCQ_EINVAL before any launch, each with a message of its own: a NULL block, N outside
+ * 2 .. 32 (33 .. 64 named as this build's limit), n_queens outside 2 .. N^3 - 1 (0 = N^2), n_chains outside 1 .. 2^31 - 1, a negative
+ * n_iters or first_iter, first_iter + n_iters >= 2^63, a move other than the two above, n_ranks outside 0 .. Q - 1, a NULL rank_cdf
+ * with n_ranks > 0, a NULL seeds, state_in or state_out, hist_stride below n_iters + 1 when energy_hist is given, a best_state that
+ * is state_in or state_out, and a chain above MCQ_MAX_EO3D_LDS (no shape in range is).  The entries of rank_cdf cannot be looked at
+ * here: they are the caller's, and the count of item 4 is defined for any of them. */
+int mcq_eo3d_device(const mcq_eo3d* q, void* hip_stream);
+/* The same rule in plain host code over HOST buffers -- an explicit stable sort of the queens in every iteration and a loop over the
+ * cells for the target --, same refusals; needs no GPU.  It also reads rank_cdf and refuses a table that decreases.  Equal to the
+ * kernel bit for bit on every output. */
+int mcq_eo3d_host(const mcq_eo3d* q);
+
 /* ---- exported by libmcq_oracle.so (tests / smoke / cpu_baseline only) --------------------- */
 
 /* CPU restatement of the reference; host buffers; n_threads <= 1 runs chains in the calling thread. */

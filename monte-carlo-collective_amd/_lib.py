@@ -152,6 +152,14 @@ SEARCH_FEATURES = {
 }
 
 
+# The full_3d forms of the searches of SEARCH_FEATURES: a sixth table of the same form, because tests/test_eo_host.py pins the keys of
+# SEARCH_FEATURES and the value of declared_features().  lib() and the loop that makes the callables walk all six through
+# linked_features(); a new full_3d search goes here.
+SEARCH3D_FEATURES = {
+    "eo3d": Feature(abi.Eo3d, "eo3d", ("eo3d_host", "eo3d_device")),
+}
+
+
 def all_features():
     """The rows of FEATURES and MORE_FEATURES, in that order."""
     return list(FEATURES.values()) + list(MORE_FEATURES.values())
@@ -168,8 +176,13 @@ def bound_features():
 
 
 def declared_features():
-    """The rows of all five tables: bound_features() and then SEARCH_FEATURES.  What lib() declares and what has a callable here."""
+    """The rows of the first five tables: bound_features() and then SEARCH_FEATURES."""
     return bound_features() + list(SEARCH_FEATURES.values())
+
+
+def linked_features():
+    """The rows of all six tables: declared_features() and then SEARCH3D_FEATURES.  What lib() declares and what has a callable here."""
+    return declared_features() + list(SEARCH3D_FEATURES.values())
 
 
 def lib():
@@ -248,7 +261,7 @@ def lib():
         L.mcq_resample_device.argtypes = [C.POINTER(abi.Resample), C.c_void_p, C.c_size_t, C.c_void_p]
         L.mcq_resample_plan_host.restype = C.c_int
         L.mcq_resample_plan_host.argtypes = [C.POINTER(abi.Resample)]
-        for f in declared_features():
+        for f in linked_features():
             getattr(L, f"mcq_{f.prefix}_last_error").restype = C.c_char_p
             for name in f.entries:  # (struct*) for a host entry, (struct*, hipStream_t) for a device entry
                 fn = getattr(L, "mcq_" + name)
@@ -262,7 +275,7 @@ def lib():
 
 def _raise(rc, last_error):
     """Nothing for abi.OK; otherwise the exception of a return code, with the text `last_error()` holds: the library keeps one
-    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES, SAMPLER3D_FEATURES, SEARCH_FEATURES), and a call's text is read from its own."""
+    thread-local message for the sweep (mcq_last_error) and one per feature (FEATURES, MORE_FEATURES, SAMPLER_FEATURES, SAMPLER3D_FEATURES, SEARCH_FEATURES, SEARCH3D_FEATURES), and a call's text is read from its own."""
     if rc == abi.OK:
         return
     msg = last_error().decode(errors="replace")
@@ -297,7 +310,7 @@ def _entry(feature, name):
     return call
 
 
-for _feature in declared_features():
+for _feature in linked_features():
     for _name in _feature.entries:
         globals()[_name] = _entry(_feature, _name)
 

@@ -647,6 +647,56 @@ def eo_lds_bytes(N):
     return NP * NP * (4 * ((NP // 4) | 1) + 6)
 
 
+EO3D_MOVE_BEST = 0             # include/mcq.h: MCQ_EO3D_MOVE_BEST
+EO3D_MOVE_RANDOM = 1           # MCQ_EO3D_MOVE_RANDOM
+MAX_EO3D_LDS = 160 * 1024      # MCQ_MAX_EO3D_LDS
+EO3D_REPEATED = 1              # MCQ_EO3D_REPEATED: bit 0 of flags
+
+
+class Eo3d(C.Structure):
+    """include/mcq.h: mcq_eo3d -- extremal optimisation of full_3d placements: the queen at a drawn rank of local badness moves to a free cell, whatever it costs"""
+    _fields_ = [
+        ("N", C.c_int32),
+        ("n_queens", C.c_int32),
+        ("n_chains", C.c_int64),
+        ("n_iters", C.c_int64),
+        ("first_iter", C.c_int64),
+        ("move", C.c_int32),
+        ("n_ranks", C.c_int32),
+        ("seeds", C.c_void_p),
+        ("rank_cdf", C.c_void_p),
+        ("state_in", C.c_void_p),
+        ("state_out", C.c_void_p),
+        ("best_floor", C.c_void_p),
+        ("energy_in", C.c_void_p),
+        ("energy_out", C.c_void_p),
+        ("best_energy", C.c_void_p),
+        ("best_iter", C.c_void_p),
+        ("best_state", C.c_void_p),
+        ("n_moves", C.c_void_p),
+        ("n_uphill", C.c_void_p),
+        ("n_flat", C.c_void_p),
+        ("n_free", C.c_void_p),
+        ("n_idle", C.c_void_p),
+        ("energy_hist", C.c_void_p),
+        ("hist_stride", C.c_int64),
+        ("flags", C.c_void_p),
+    ]
+
+
+# the per-chain outputs of a full_3d extremal-optimisation call besides the placements (state, best_state): field -> dtype
+# ("energy_hist" has a row of n_iters + 1 per chain)
+EO3D_DTYPES = dict(EO_DTYPES, flags=np.int32)
+
+
+def eo3d_lds_bytes(N, Q=None):
+    """The bytes of LDS a chain of mcq_eo3d_device takes (include/mcq.h, below the rule); every shape stays within MAX_EO3D_LDS."""
+    N = int(N)
+    Q = N * N if Q is None or int(Q) == 0 else int(Q)
+    cells, cpd = N ** 3, 4 if N <= 19 else 2
+    return 4 * (480 + -(-cells // cpd) + -(-cells // 32) + (Q + 1) // 2)
+
+
 MAX_HEATBATH_TABLE = 512       # include/mcq.h: MCQ_MAX_HEATBATH_TABLE
 HEATBATH_WEIGHT_BITS = 24      # MCQ_HEATBATH_WEIGHT_BITS
 MAX_N_HEATBATH_COUNTERS = 16   # MCQ_MAX_N_HEATBATH_COUNTERS: the largest N of mcq_heatbath_counters_device

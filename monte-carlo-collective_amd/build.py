@@ -48,6 +48,9 @@ NFOLD3D_SOURCES = [os.path.join(CSRC, "mcq_nfold3d.hip")]
 # extremal optimisation of board placements, a rank draw over the local badness of the columns on the board table: a fourteenth list, as
 # tests pin the thirteen above; compiled into the same library
 EO_SOURCES = [os.path.join(CSRC, "mcq_eo.hip")]
+# extremal optimisation of full_3d placements, a rank draw over the local badness of the queens on one attack field: a fifteenth list,
+# as tests pin the fourteen above; compiled into the same library
+EO3D_SOURCES = [os.path.join(CSRC, "mcq_eo3d.hip")]
 # what the sources include: the C-ABI; the chain record of the sweep and the resume kernels; the attack field of the full_3d files;
 # what the four files outside the sweep (the quenches and the heat baths) share beyond it; the lane helpers of the board heat-bath column
 # update, which the tempered sweep shares; the board table of the pair-move quench, the board hops and the board tabu search
@@ -70,7 +73,7 @@ def stale():
     if not os.path.exists(SO):
         return True
     t = os.path.getmtime(SO)
-    if any(os.path.getmtime(f) > t for f in RELINK_SOURCES + RELINK3D_SOURCES + NFOLD_SOURCES + NFOLD3D_SOURCES + EO_SOURCES):
+    if any(os.path.getmtime(f) > t for f in RELINK_SOURCES + RELINK3D_SOURCES + NFOLD_SOURCES + NFOLD3D_SOURCES + EO_SOURCES + EO3D_SOURCES):
         return True
     return any(os.path.getmtime(f) > t for f in SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + TABU3D_SOURCES + HEADERS)
 
@@ -80,7 +83,7 @@ def build(force=False, verbose=False):
     if not force and not stale():
         return SO
     cmd = [hipcc()] + FLAGS + ["-o", SO] + SOURCES + ADDED_SOURCES + TEMPER_SOURCES + TEMPER3D_SOURCES + PAIRS_SOURCES + HOP_SOURCES + HOP3D_SOURCES + TABU_SOURCES + TABU3D_SOURCES
-    cmd += RELINK_SOURCES + RELINK3D_SOURCES + NFOLD_SOURCES + NFOLD3D_SOURCES + EO_SOURCES
+    cmd += RELINK_SOURCES + RELINK3D_SOURCES + NFOLD_SOURCES + NFOLD3D_SOURCES + EO_SOURCES + EO3D_SOURCES
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + r.stdout + r.stderr)
