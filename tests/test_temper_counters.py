@@ -13,6 +13,7 @@ import pytest
 import mcq_amd
 from tests import heatbath_counters_util as cu
 from tests import quench_util as qu
+from tests import temper_tables_util as tt
 from tests import temper_util as tu
 
 abi = mcq_amd.abi
@@ -56,17 +57,6 @@ def _same(got, want, what, hist):
     assert set(got) == set(want), what
     for k in want:
         assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, (what, k)
-
-
-def _own_tables(N, s, seeds, T, X, K, first, rungs=None, form="counters"):
-    """temper_device with the caller's own tables (NumPy uint32), traced, as NumPy arrays."""
-    import torch
-
-    dev = torch.device("cuda", torch.cuda.current_device())
-    tabs = (torch.from_numpy(T.view(np.int32)).to(dev), torch.from_numpy(X.view(np.int32)).to(dev))
-    res = tempering.temper_device(N, torch.from_numpy(s).to(dev), seeds, tables=tabs, exchange_every=K, first_sweep=first, rungs=rungs, trace=True, form=form)
-    torch.cuda.current_stream(dev).synchronize()
-    return tempering.to_numpy(res)
 
 
 @pytest.mark.parametrize("N", range(2, 17))
@@ -130,7 +120,7 @@ def test_the_largest_lds_footprint():
         n = R * ladders
         s, seeds, rungs = _boards(N, n, 16 + ladders), _seeds(n, ladders), _rungs(n, R, ladders)
         want = tu.host_call(N, s, seeds, tab, X, K, first, rungs)
-        _same(_own_tables(N, s, seeds, tab, X, K, first, rungs), want, f"N=16 R=16 D=512, {ladders} ladders", True)
+        _same(tt.own_tables(N, s, seeds, tab, X, K, first, rungs), want, f"N=16 R=16 D=512, {ladders} ladders", True)
         assert want["n_changed"].sum() > 0
 
 
@@ -142,13 +132,13 @@ def test_a_callers_own_tables():
         s, seeds, rungs = _boards(N, n, 7 * N), _seeds(n, 1), _rungs(n, R, N)
         X = abi.temper_tables([0.2] * T, _ladder(R), K, first)[1]
         one = np.full((T, R, 1), 1 << 24, dtype=np.uint32)
-        _same(_own_tables(N, s, seeds, one, X, K, first, rungs), tu.host_call(N, s, seeds, one, X, K, first, rungs), f"N={N} R={R}, D = 1", True)
+        _same(tt.own_tables(N, s, seeds, one, X, K, first, rungs), tu.host_call(N, s, seeds, one, X, K, first, rungs), f"N={N} R={R}, D = 1", True)
         cold = np.tile(np.array([1 << 24, 0], dtype=np.uint32), (T, R, 1))
-        got = _own_tables(N, s, seeds, cold, X, K, first, rungs)
+        got = tt.own_tables(N, s, seeds, cold, X, K, first, rungs)
         _same(got, tu.host_call(N, s, seeds, cold, X, K, first, rungs), f"N={N} R={R}, T = [2^24, 0]", True)
         assert (np.diff(got["energy_hist"], axis=1) <= 0).all()
         Tt = abi.temper_tables(np.linspace(0.3, 1.0, T), _ladder(R), K, first)[0]
-        zero = _own_tables(N, s, seeds, Tt, np.zeros_like(X), K, first, rungs)
+        zero = tt.own_tables(N, s, seeds, Tt, np.zeros_like(X), K, first, rungs)
         _same(zero, tu.host_call(N, s, seeds, Tt, np.zeros_like(X), K, first, rungs), f"N={N} R={R}, X = 0", True)
         tu.check_invariants(zero, R, K, first, swap_zero=True)
 
