@@ -12,6 +12,7 @@ import pytest
 import mcq_amd
 from oracle import oracle
 from tests import near_tie_util as nt
+from tests import population_util as pu
 from tests import resume_util as ru
 from tests import util
 
@@ -124,63 +125,7 @@ def test_segments_add_the_near_ties_up(name):
 
 # ---- the fold kernel of population annealing (mcq_resample_device with state_in == NULL) ---------------------------------------------
 
-GUARD = 0xA5
-FOLD_SLOTS = 4096
-
-
-def fold_rule(first_step, seg, run):
-    """include/mcq.h, mcq_resample: a segment moves best_energy / steps_to_best (in whole-run steps) / best_state only by a STRICTLY lower
-    energy; n_accepted, near_ties and stream_words (modulo 2^32) add up; first_step == 0 copies.  `seg`, `run`: dicts of arrays; returns
-    the run's arrays after the fold."""
-    first = first_step == 0
-    lower = np.ones(len(seg["best_energy"]), dtype=bool) if first else seg["best_energy"] < run["best_energy"]
-    out = {"best_energy": np.where(lower, seg["best_energy"], run["best_energy"]).astype(np.int32),
-           "steps_to_best": np.where(lower, np.int64(first_step) + seg["steps_to_best"], run["steps_to_best"]).astype(np.int64),
-           "n_accepted": (seg["n_accepted"] + (0 if first else run["n_accepted"])).astype(np.int64)}
-    if "near_ties" in run:
-        out["near_ties"] = (seg["near_ties"] + (0 if first else run["near_ties"])).astype(np.int64)
-    if "stream_words" in run:
-        out["stream_words"] = ((seg["stream_words"].astype(np.uint64) + (0 if first else run["stream_words"].astype(np.uint64))) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-    if "best_state" in run:
-        out["best_state"] = np.where(lower[:, None], seg["best_state"], run["best_state"])
-    return out
-
-
-def fold_vectors(first_step, state_bytes, seed):
-    """Random summaries of FOLD_SLOTS slots with, in known numbers of slots: ties on both sides, stream words whose sum passes 2^32, steps
-    beyond 2^31, equal best energies, and lower ones."""
-    rs, n = np.random.RandomState(seed), FOLD_SLOTS
-    seg = {"best_energy": rs.randint(0, 60, n).astype(np.int32), "steps_to_best": rs.randint(0, 5000, n).astype(np.int64),
-           "n_accepted": rs.randint(0, 5000, n).astype(np.int64), "near_ties": np.zeros(n, dtype=np.int64),
-           "stream_words": rs.randint(0, 2**31, n).astype(np.uint32), "best_state": rs.randint(0, 256, (n, state_bytes)).astype(np.uint8)}
-    run = {"best_energy": rs.randint(0, 60, n).astype(np.int32), "steps_to_best": rs.randint(0, 2**40, n).astype(np.int64),
-           "n_accepted": rs.randint(0, 2**40, n).astype(np.int64), "near_ties": np.zeros(n, dtype=np.int64),
-           "stream_words": rs.randint(0, 2**31, n).astype(np.uint32), "best_state": rs.randint(0, 256, (n, state_bytes)).astype(np.uint8)}
-    idx = rs.permutation(n)
-    seg["near_ties"][idx[:700]] = rs.randint(1, 9, 700)                       # ties in the segment only, in the run only, on both sides
-    run["near_ties"][idx[400:1100]] = rs.randint(1, 2**33, 700)
-    wrap = idx[1100:1600]                                                     # 500 slots whose words pass 2^32
-    seg["stream_words"][wrap] = rs.randint(2**31 + 1, 2**32, 500).astype(np.uint32)
-    run["stream_words"][wrap] = rs.randint(2**31 + 1, 2**32, 500).astype(np.uint32)
-    equal = idx[1600:2100]                                                    # 500 ties of the best energy: the run's values stay
-    seg["best_energy"][equal] = run["best_energy"][equal]
-    lower = idx[2100:2600]                                                    # 500 strictly lower: all three move
-    seg["best_energy"][lower] = run["best_energy"][lower] - rs.randint(1, 5, 500).astype(np.int32)
-    seg["steps_to_best"][idx[2600:3100]] = rs.randint(2**31, 2**33, 500)     # a segment's own step beyond 2^31
-    counts = {"seg_ties": int((seg["near_ties"] > 0).sum()), "run_ties": int((run["near_ties"] > 0).sum()),
-              "both_ties": int(((seg["near_ties"] > 0) & (run["near_ties"] > 0)).sum()),
-              "wraps": int((seg["stream_words"].astype(np.uint64) + run["stream_words"].astype(np.uint64) >= 2**32).sum()),
-              "equal": int((seg["best_energy"] == run["best_energy"]).sum()), "lower": int((seg["best_energy"] < run["best_energy"]).sum()),
-              "far_steps": int((np.int64(first_step) + seg["steps_to_best"] > 2**31).sum())}
-    return seg, run, counts
-
-
-def _guarded(torch, dev, a):
-    """`a` on the device between two guard blocks of 64 bytes: (tensor of everything, view of the array)."""
-    raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-    buf = torch.full((raw.size + 128,), GUARD, dtype=torch.uint8, device=dev)
-    buf[64: 64 + raw.size] = torch.from_numpy(raw.copy()).to(dev)
-    return buf, buf[64: 64 + raw.size]
+GUARD, fold_rule, fold_vectors, _guarded = pu.GUARD, pu.fold_rule, pu.fold_vectors, pu.guarded  # (shared with tests/test_population.py)
 
 
 def _fold_on_device(first_step, seg, run, state_bytes, optional=("near_ties", "stream_words", "best_state"), half=None):

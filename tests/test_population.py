@@ -1,6 +1,7 @@
 """GPU: population annealing (mcq_resample_device through population.anneal_population) against the NumPy restatement of the rule, against
 a run composed on the host from _lib.run_host_from segments, and -- where every plan is the identity -- against the CPU oracle's
-unbroken chains.  Everything is bit for bit."""
+unbroken chains; the four resampling kernels directly, at every kind of population size and table and in the one call the driver makes at a
+boundary, between guard bytes.  Everything is bit for bit."""
 import ctypes
 import os
 import subprocess
@@ -58,6 +59,114 @@ def test_plan_kernel_equals_the_restatement():
         host_p, host_s = mcq_amd._lib.resample_plan_host(e, R, tab, x)
         np.testing.assert_array_equal(got_p, host_p, err_msg=f"{name}: kernel vs host code")
         np.testing.assert_array_equal(got_s, host_s, err_msg=f"{name}: kernel vs host code, stats")
+
+
+RUN_FIELDS = ("best_energy", "steps_to_best", "n_accepted", "near_ties", "stream_words", "best_state")
+
+
+def _guarded_call(energies, R, tab, offsets, state, first_step=0, seg=None, run=None, energy_out=True, fold=True, best_state=True):
+    """One mcq_resample_device call as anneal_population issues it: plan, gather and (with seg / run) the fold in one call.  The scratch is
+    exactly mcq_resample_scratch_bytes, and it and every array sit between 64-byte guard blocks, checked afterwards; every input, and
+    every array the call was not given, must come back unchanged.  Returns the written arrays as NumPy arrays."""
+    import torch
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    st = torch.cuda.current_stream(dev)
+    n, sb = len(energies), state.shape[1]
+    ins = {"energies": np.ascontiguousarray(energies, dtype=np.int32), "table": np.ascontiguousarray(tab, dtype=np.uint32),
+           "offsets": np.ascontiguousarray(offsets, dtype=np.uint32), "state_in": np.ascontiguousarray(state, dtype=np.uint8)}
+    outs = {"parent": np.full(n, -1, dtype=np.int32), "stats": np.full((n // R, 3), -1, dtype=np.int64),
+            "state_out": np.full((n, sb), 0xEE, dtype=np.uint8), "energy_out": np.full(n, -1, dtype=np.int32)}
+    for side, d in (("seg", seg), ("run", run)):
+        for k in (d or {}):
+            (ins if side == "seg" else outs)[f"{side}_{k}"] = d[k]
+    r = abi.Resample()
+    r.n_chains, r.population, r.state_bytes, r.table_len, r.first_step = n, R, sb, len(tab), int(first_step)
+    absent = {k for k in outs if k.startswith("run_") and not fold} | {k for k in list(ins) + list(outs) if k.endswith("_best_state") and not best_state}
+    absent |= set() if energy_out else {"energy_out"}
+    bufs = {k: pu.guarded(torch, dev, a) for k, a in {**ins, **outs}.items()}
+    for k, (_, view) in bufs.items():
+        if k not in absent:
+            setattr(r, k, view.data_ptr())
+    exact = int(mcq_amd._lib.lib().mcq_resample_scratch_bytes(ctypes.byref(r)))
+    assert exact == 8 * n
+    bufs["scratch"] = pu.guarded(torch, dev, np.zeros(exact, dtype=np.uint8))
+    assert bufs["scratch"][1].data_ptr() % 8 == 0 and all(bufs[k][1].data_ptr() % 16 == 0 for k in bufs)
+    before = {k: buf.cpu().numpy().copy() for k, (buf, _) in bufs.items()}
+    assert bufs["scratch"][1].numel() == exact
+    mcq_amd._lib.resample_device(r, bufs["scratch"][1], st)
+    st.synchronize()
+    got = {}
+    for k, (buf, _) in bufs.items():
+        now = buf.cpu().numpy()
+        assert (now[:64] == pu.GUARD).all() and (now[-64:] == pu.GUARD).all(), f"guard bytes around {k} were written"
+        if k in ins or k in absent:
+            np.testing.assert_array_equal(now, before[k], err_msg=f"{k} must not be written")
+        if k in outs:
+            got[k] = now[64:-64].view(outs[k].dtype).reshape(outs[k].shape).copy()
+    return got
+
+
+@pytest.mark.parametrize("group", pu.WIDE_GROUPS)
+def test_plan_kernels_equal_the_restatement_on_the_wide_vectors(group):
+    """The scan and the search kernel on tests/population_util.wide_vector_list(), whose conditions wide_plans() has asserted from the
+    restatement: parents, all of stats and the gathered energies, against the restatement and against the host code.  The rows are each
+    slot's own index, so state_out is the parents once more."""
+    for v, want_p, want_s in pu.wide_plans():
+        if v.group != group:
+            continue
+        n = len(v.energies)
+        own = np.arange(n, dtype=np.int32)
+        got = _guarded_call(v.energies, v.R, v.table, v.offsets, own.view(np.uint8).reshape(n, 4))
+        np.testing.assert_array_equal(got["parent"], want_p, err_msg=f"{v.name}: parents")
+        np.testing.assert_array_equal(got["stats"], want_s, err_msg=f"{v.name}: distinct parents, W, E_min")
+        np.testing.assert_array_equal(got["energy_out"], v.energies[want_p], err_msg=f"{v.name}: gathered energies")
+        np.testing.assert_array_equal(got["state_out"].view(np.int32).ravel(), want_p, err_msg=f"{v.name}: gathered rows")
+        host_p, host_s = mcq_amd._lib.resample_plan_host(v.energies, v.R, v.table, v.offsets)
+        np.testing.assert_array_equal(got["parent"], host_p, err_msg=f"{v.name}: kernel vs host code")
+        np.testing.assert_array_equal(got["stats"], host_s, err_msg=f"{v.name}: kernel vs host code, stats")
+
+
+def _boundary(first_step, state_bytes, **absent):
+    """The boundary call on tests/population_util.boundary_vectors() and what the rule expects of it: (got, want, vectors)."""
+    v = pu.boundary_vectors(first_step, state_bytes, seed=first_step % 1000 + state_bytes)
+    c = v["counts"]
+    assert len(v["energies"]) == 4160 and v["R"] == 1040 and c["equal"] >= 500 and c["lower"] >= 500 and c["moved"] >= 500, c
+    got = _guarded_call(v["energies"], v["R"], v["table"], v["offsets"], v["state"], first_step, v["seg"], v["run"], **absent)
+    p = v["parent"]
+    want = {"parent": p, "stats": v["stats"], "state_out": v["state"][p], "energy_out": v["energies"][p]}
+    want.update({f"run_{k}": a for k, a in pu.fold_rule(first_step, v["seg"], v["run"]).items()})
+    return got, want, v
+
+
+@pytest.mark.parametrize("first_step", (0, 5000))
+@pytest.mark.parametrize("state_bytes", (36, 81, 144))
+def test_boundary_call_as_the_driver_issues_it(first_step, state_bytes):
+    """Plan, gather, the fold of best_state in the same rows kernel and the scalar fold in ONE call: 4 populations of 1 040 slots, rows of
+    36, 81 and 144 bytes (4-, 1- and 16-byte lanes).  best_state is decided on the run's OLD best_energy although the scalar fold of the same
+    call rewrites it: strictly lower moves the row, equal keeps it."""
+    got, want, v = _boundary(first_step, state_bytes)
+    assert sorted(got) == sorted(want) and all(("run_" + k) in want for k in RUN_FIELDS)
+    if first_step:
+        eq, lo = v["seg"]["best_energy"] == v["run"]["best_energy"], v["seg"]["best_energy"] < v["run"]["best_energy"]
+        assert (want["run_best_state"][eq] == v["run"]["best_state"][eq]).all() and (want["run_best_state"][lo] == v["seg"]["best_state"][lo]).all()
+        assert (want["run_best_energy"][lo] == v["seg"]["best_energy"][lo]).all()
+    for k in want:
+        np.testing.assert_array_equal(got[k], want[k], err_msg=f"first_step {first_step}, rows of {state_bytes} bytes: {k}")
+
+
+@pytest.mark.parametrize("absent", ("energy_out", "fold", "best_state"))
+def test_boundary_call_leaves_absent_arrays_alone(absent):
+    """The same call without energy_out, without the fold (run_* NULL: nothing of the run is written) and without seg / run_best_state
+    while the scalars fold: the rest follows the rule, and what was not given is not written (_guarded_call checks it byte for byte)."""
+    got, want, v = _boundary(5000, 81, **{absent: False})
+    untouched = {"energy_out": ("energy_out",), "fold": tuple("run_" + k for k in RUN_FIELDS), "best_state": ("run_best_state",)}[absent]
+    for k in want:
+        if k not in untouched:
+            np.testing.assert_array_equal(got[k], want[k], err_msg=f"without {absent}: {k}")
+    for k in untouched:
+        given = np.full(len(v["energies"]), -1, dtype=np.int32) if k == "energy_out" else v["run"][k[4:]]
+        np.testing.assert_array_equal(got[k], given, err_msg=f"without {absent}: {k} was written")
 
 
 def test_gather_kernel_moves_the_parents_rows():

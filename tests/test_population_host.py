@@ -39,10 +39,61 @@ def test_host_plan_equals_the_restatement():
             np.testing.assert_array_equal(got_p, np.arange(len(e)), err_msg=f"{name}: equal weights give the identity")
 
 
+def test_exact_restatement_returns_what_the_int64_one_did():
+    """plan() in uint64 / Python ints against its former int64 self, on every vector that one could describe."""
+    for name, e, R, tab, x in pu.plan_vectors():
+        want_p, want_s = pu.plan_int64(e, R, tab, x)
+        got_p, got_s = pu.plan(e, R, tab, x)
+        assert got_p.dtype == want_p.dtype and got_s.dtype == want_s.dtype
+        np.testing.assert_array_equal(got_p, want_p, err_msg=f"{name}: parents")
+        np.testing.assert_array_equal(got_s, want_s, err_msg=f"{name}: distinct parents, W, E_min")
+    # ... and where that one could not go: R W = 2^62 exactly (R = 2^19 chains of full weight) is the identity
+    R = 1 << 19
+    p, s = pu.plan(np.zeros(R, dtype=np.int32), R, pu.table(0.0), [2**32 - 1])
+    assert R * int(s[0, 1]) == 2**62 and (p == np.arange(R)).all() and int(s[0, 0]) == R
+
+
+def test_host_plan_equals_the_restatement_on_the_wide_vectors():
+    """mcq_resample_plan_host on tests/population_util.wide_vector_list(): ragged wavefronts and tiles up to MCQ_MAX_POPULATION, caller's
+    tables (W = 0 among them), the whole int32 range, entries up to 2^32.  wide_plans() asserts every vector's condition first."""
+    plans = pu.wide_plans()
+    assert {v.group for v, _, _ in plans} == set(pu.WIDE_GROUPS) and {v.R for v, _, _ in plans} >= set(pu.WIDE_SIZES)
+    assert abi.MAX_POPULATION == max(pu.WIDE_SIZES)
+    for v, want_p, want_s in plans:
+        got_p, got_s = mcq_amd._lib.resample_plan_host(v.energies, v.R, v.table, v.offsets)
+        np.testing.assert_array_equal(got_p, want_p, err_msg=f"{v.name}: parents")
+        np.testing.assert_array_equal(got_s, want_s, err_msg=f"{v.name}: distinct parents, W, E_min")
+        pu.assert_plan_properties(v.energies, v.R, v.table, got_p, v.name)
+
+
+def test_vectorised_properties_agree_with_the_walk():
+    """Both forms pass the host plan of every existing vector up to R = 1 024, and both refuse the same spoilt plans."""
+    for name, e, R, tab, x in pu.plan_vectors():
+        if R > 1024:
+            continue
+        p, _ = mcq_amd._lib.resample_plan_host(e, R, tab, x)
+        pu.assert_plan_properties(e, R, tab, p, name)
+        pu.assert_plan_properties_walk(e, R, tab, p, name)
+        spoilt = []
+        if (p != np.arange(len(e))).any():
+            spoilt.append(np.arange(len(e), dtype=np.int32))                # the identity where the rule moves something
+        spoilt.append(np.concatenate([p[:1], p[:-1]]).astype(np.int32))     # shifted by one slot
+        spoilt.append(np.where(np.arange(len(e)) % R == R - 1, p - (p % R), p).astype(np.int32))  # the last slot of a population: not monotone
+        for q in spoilt:
+            if (q == p).all():
+                continue
+            verdicts = []
+            for check in (pu.assert_plan_properties, pu.assert_plan_properties_walk):
+                try:
+                    check(e, R, tab, q, name)
+                    verdicts.append(None)
+                except AssertionError as err:
+                    verdicts.append(str(err))
+            assert verdicts[0] == verdicts[1], f"{name}: the vectorised check says {verdicts[0]!r}, the walk {verdicts[1]!r}"
+
+
 def test_plan_properties():
     for name, e, R, tab, x in pu.plan_vectors():
-        if R == 65536 and not name.startswith(("bimodal", "one chain", "mild")):
-            continue  # (the Python-int walk over 65 536 chains is slow: three vectors of that size)
         got_p, got_s = mcq_amd._lib.resample_plan_host(e, R, tab, x)
         pu.assert_plan_properties(e, R, tab, got_p, name)
         assert all(int(got_s[g, 0]) == len(np.unique(got_p[g * R: (g + 1) * R])) for g in range(len(e) // R)), name
